@@ -7,6 +7,17 @@ ranks when N > 1).  The optimizer is excluded, as the metric defines.
 value = frames (B*T per rank, all ranks) / max-over-ranks wall time of K steps.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5]
+                  [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: set up, W warm-up steps,
+K timed steps, one JSON line (metric, value, unit, ms_per_step, ...).
+--dump-outputs DIR then writes what the last timed step computed (logits,
+values, the flat gradient buffer) as DIR/<name>.npy; the inputs are seeded, so
+two builds run with the same arguments can be compared output for output.
+--full adds everything else to the line: the library's per-kernel HIP events in
+the last timed step(s) and the roofline figures made from them, the per-bucket
+all-reduce times (N > 1), the fused-Adam timing, the drop-in API and episode
+legs and the CPU baselines (each with its own --no-* switch).
 
 N > 1 is launched by the driver with torch.distributed.run (one rank per GPU,
 RCCL).  Rank 0 prints ONE JSON line.  Inputs are synthetic (seeded uint8
@@ -325,6 +336,13 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's logits, values and flat gradients "
+                         "as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: per-kernel HIP events and roofline, "
+                         "all-reduce bucket times, fused Adam, the drop-in API and episode legs, the CPU baselines "
+                         "(the --no-* and --timed-steps switches below apply to such a run)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-dropin", action="store_true", help="skip the drop-in Agent API measurement")
     ap.add_argument("--no-overlap", action="store_true")
@@ -385,7 +403,9 @@ def main():
     # live in the LAST timed step only: an event pair around every launch of
     # every step costs ~7 % of the step time at C2 (4.85 vs 4.54 ms/step,
     # tools/ab_timing.sh), so the sample keeps that cost to 1/K of it.
-    timed = 0 if args.no_kernel_timing else max(1, min(args.timed_steps, args.steps))
+    # A plain run (no --full) records none: only the wall time of the K steps.
+    timed = max(1, min(args.timed_steps, args.steps)) if args.full and not args.no_kernel_timing else 0
+    result = None
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -394,15 +414,23 @@ def main():
         last = i == args.steps - 1
         if timed and i == args.steps - timed:
             N.timing_enable(True)
-        learner.step(frames, dl, dv, overlap=not args.no_overlap, comm_timing=last and world > 1)
+        result = learner.step(frames, dl, dv, overlap=not args.no_overlap,
+                              comm_timing=last and world > 1 and args.full)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    allk = {k: N.timing_stats(k) for k in range(N.TIMER_N)}
-    kt = {k: allk[k] for k in (N.TIMER_FWD_STEP, N.TIMER_BPTT_STEP, N.TIMER_CORE_WGRAD)}
-    ka = {k: allk[k] for k in (N.TIMER_ATTN_FWD, N.TIMER_ATTN_BWD)}
-    N.timing_enable(False)
+    if timed:
+        allk = {k: N.timing_stats(k) for k in range(N.TIMER_N)}
+        kt = {k: allk[k] for k in (N.TIMER_FWD_STEP, N.TIMER_BPTT_STEP, N.TIMER_CORE_WGRAD)}
+        ka = {k: allk[k] for k in (N.TIMER_ATTN_FWD, N.TIMER_ATTN_BWD)}
+        N.timing_enable(False)
+    if args.dump_outputs and rank == 0 and result is not None:
+        # what a caller of Learner.step receives from the last timed step: its return value and the
+        # gradient buffer it filled (state_dict order, flat; all-reduced over the ranks when N > 1)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, t in (("logits", result[0]), ("values", result[1]), ("grads", learner.grads)):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), t.detach().float().cpu().numpy())
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -410,10 +438,32 @@ def main():
     ms = elapsed / args.steps * 1e3
     frames_total = B * T * world * args.steps
     value = frames_total / elapsed
-    if args.no_kernel_timing:
+    if args.full and args.no_kernel_timing:
         if rank == 0:
             print(json.dumps({"metric": METRIC, "value": round(value, 2), "unit": "frames/s", "n_gpus": world,
                               "steps": args.steps, "ms_per_step": round(ms, 3), "kernel_timing": False}), flush=True)
+        return
+    head = {
+        "metric": METRIC, "value": round(value, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": dtype,
+        "data": ("synthetic: seeded uint8 frames resident in HBM, cast to fp32 (raw 0..255) inside the first "
+                 "kernel" if args.frames == "u8" else "synthetic: seeded uint8 frames cast to fp32 (raw 0..255) on "
+                 "the host") + ", seeded uniform weights of the reference architecture, N(0,1) logits/values "
+                 "cotangents (seeds 2, 3)",
+        "config": {"workload": cfg["desc"], "global_batch": B * world, "seq_len": T, "frame": f"{H}x{W}",
+                   "heads": nq, "parallelism": f"dp{world}",
+                   **({"arithmetic": "fp32 operands split into three bf16 parts (8+8+8 mantissa bits), six products "
+                                     "per fp32 product on the bf16 MFMA, fp32 accumulation (gemm.h SPLIT6); error vs "
+                                     "the fp64 evaluation within 2x of the fp32 MFMA's "
+                                     "(tests/test_gpu_parity.py::test_f32_split6_accuracy); roofline peak = bf16 "
+                                     "dense / 6"} if split6_on(dtype) else {})},
+    }
+    if not args.full:   # the headline figure alone; everything below takes events or runs of its own
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
         return
 
     # roofline of the dominant kernel class (largest total device time): the
@@ -460,20 +510,7 @@ def main():
                         "remainder is launch gaps, host enqueue and the unattributed memsets"}
 
     out = {
-        "metric": METRIC, "value": round(value, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": dtype,
-        "data": ("synthetic: seeded uint8 frames resident in HBM, cast to fp32 (raw 0..255) inside the first "
-                 "kernel" if args.frames == "u8" else "synthetic: seeded uint8 frames cast to fp32 (raw 0..255) on "
-                 "the host") + ", seeded uniform weights of the reference architecture, N(0,1) logits/values "
-                 "cotangents (seeds 2, 3)",
-        "config": {"workload": cfg["desc"], "global_batch": B * world, "seq_len": T, "frame": f"{H}x{W}",
-                   "heads": nq, "parallelism": f"dp{world}",
-                   **({"arithmetic": "fp32 operands split into three bf16 parts (8+8+8 mantissa bits), six products "
-                                     "per fp32 product on the bf16 MFMA, fp32 accumulation (gemm.h SPLIT6); error vs "
-                                     "the fp64 evaluation within 2x of the fp32 MFMA's "
-                                     "(tests/test_gpu_parity.py::test_f32_split6_accuracy); roofline peak = bf16 "
-                                     "dense / 6"} if split6_on(dtype) else {})},
+        **head,
         "roofline": {"bound": "mfma", "kernel": names[dom], "variant": d["variant"], "achieved": round(achieved, 2),
                      "peak": peak, "unit": "TFLOP/s", "frac": round(achieved / peak, 4),
                      **pmc_traffic(args.config, world, d["variant"]),

@@ -40,7 +40,7 @@ def test_bench_two_ranks_line(config, b, variant):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr=127.0.0.1", f"--master-port={_port()}", os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--steps", "3", "--warmup", "2", "--config", config, "--batch", str(b),
-           "--backend", "gloo", "--same-device"]
+           "--backend", "gloo", "--same-device", "--full"]   # --full: the comm block and the kernel table
     env = dict(os.environ, OMP_NUM_THREADS="2")
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out; mkdir -p $O; cd $R
 i=0
 for spec in "$@"; do
   i=$((i+1))
-  env $spec timeout -k 10 300 python bench.py --no-cpu-baseline --steps 20 ${BENCH_ARGS} > $O/abenv_$i.json 2>/dev/null; rc=$?; [ $rc -eq 0 ] || { echo "bench [$spec] rc=$rc"; exit $rc; }
+  env $spec timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 20 ${BENCH_ARGS} > $O/abenv_$i.json 2>/dev/null; rc=$?; [ $rc -eq 0 ] || { echo "bench [$spec] rc=$rc"; exit $rc; }
   python -c "import json;d=json.load(open('$O/abenv_$i.json'));print('[$spec]',d['value'],d['ms_per_step'],json.dumps(d['kernels']))"
   if [ "$PROF" = "1" ]; then
     rm -rf $O/abprof_$i

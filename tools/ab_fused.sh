@@ -6,6 +6,6 @@ for t in 9 12 13 14 15 16; do
 done
 echo parity ok
 for c in "$@"; do for t in 9 12 13 14 15 16; do
-  AAA_FUSED_TILE=$t timeout -k 10 200 python bench.py --config $c --no-cpu-baseline --steps 10 > $O/ab_${c}_f$t.json 2>/dev/null || exit 1
+  AAA_FUSED_TILE=$t timeout -k 10 200 python bench.py --full --config $c --no-cpu-baseline --steps 10 > $O/ab_${c}_f$t.json 2>/dev/null || exit 1
   python -c "import json;d=json.loads(open('$O/ab_${c}_f$t.json').read().strip().splitlines()[-1]);k=d['kernels'];print('$c ftile=$t',d['value'],[(n[:20],v['avg_us']) for n,v in k.items()])"
 done; done

@@ -6,6 +6,6 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out; mkdir -p $O; cd $R
 i=0
 for lib in "$@"; do
   i=$((i+1))
-  AAA_LIB=$lib timeout -k 10 300 python bench.py --no-cpu-baseline --steps 20 ${BENCH_ARGS} > $O/ablib_$i.json 2>/dev/null; rc=$?; [ $rc -eq 0 ] || { echo "bench [$lib] rc=$rc"; exit $rc; }
+  AAA_LIB=$lib timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 20 ${BENCH_ARGS} > $O/ablib_$i.json 2>/dev/null; rc=$?; [ $rc -eq 0 ] || { echo "bench [$lib] rc=$rc"; exit $rc; }
   python -c "import json;d=json.load(open('$O/ablib_$i.json'));print('[$lib]',d['value'],d['ms_per_step'],json.dumps(d['kernels']))"
 done

@@ -15,7 +15,7 @@ for c in "$@"; do
   for arm in $LIBS; do
     i=$((i+1)); lib=${arm%%@*}; envs=""
     [ "$arm" != "$lib" ] && envs=$(echo "${arm#*@}" | tr ',' ' ')
-    env $envs AAA_LIB=$R/$lib timeout -k 10 300 python bench.py --config $c --no-cpu-baseline --no-dropin --no-episode --steps 10 > $O/ab_${c}_$i.json 2> $O/ab_${c}_$i.err || { echo "bench $c [$lib] rc=$?"; tail $O/ab_${c}_$i.err; exit 1; }
+    env $envs AAA_LIB=$R/$lib timeout -k 10 300 python bench.py --full --config $c --no-cpu-baseline --no-dropin --no-episode --steps 10 > $O/ab_${c}_$i.json 2> $O/ab_${c}_$i.err || { echo "bench $c [$lib] rc=$?"; tail $O/ab_${c}_$i.err; exit 1; }
     python -c "import json;d=json.loads(open('$O/ab_${c}_$i.json').read().strip().splitlines()[-1]);print('$c [$arm]',d['value'],d['ms_per_step'],[(n[:22],v.get('avg_us',v.get('ms')),v.get('frac')) for n,v in d['kernels'].items()],[(n[:18],v['avg_us']) for n,v in d['hbm_kernels'].items()])"
   done
 done

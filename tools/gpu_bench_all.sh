@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out; mkdir -p $O; cd $R
 first=$1
 for c in "$@"; do
   extra=""; [ "$c" != "$first" ] && extra="--no-cpu-baseline"
-  timeout -k 10 300 python bench.py --config $c $extra > $O/bench_$c.json 2> $O/bench_$c.err || { echo "bench $c rc=$?"; tail $O/bench_$c.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --config $c $extra > $O/bench_$c.json 2> $O/bench_$c.err || { echo "bench $c rc=$?"; tail $O/bench_$c.err; exit 1; }
   python -c "import json;d=json.loads(open('$O/bench_$c.json').read().strip().splitlines()[-1]);print('$c',d['value'],d['ms_per_step'],d['roofline']['frac'],d['roofline']['avg_launch_us'],json.dumps(d['hbm_kernels']))"
 done
 cd /tmp && export TMPDIR=/tmp

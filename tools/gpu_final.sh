@@ -8,7 +8,7 @@ timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.
 tail -1 $O/smoke.log
 for c in c2 c3 c4 c5; do
   extra=""; [ $c != c2 ] && extra="--no-cpu-baseline"
-  timeout -k 10 300 python bench.py --config $c $extra > $O/bench_$c.json 2> $O/bench_$c.err || { echo "bench $c rc=$?"; tail $O/bench_$c.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --config $c $extra > $O/bench_$c.json 2> $O/bench_$c.err || { echo "bench $c rc=$?"; tail $O/bench_$c.err; exit 1; }
   python -c "import json;d=json.loads(open('$O/bench_$c.json').read().strip().splitlines()[-1]);print('$c',d['value'],d['ms_per_step'],d['roofline']['kernel'],d['roofline']['frac'])"
 done
 cd /tmp && export TMPDIR=/tmp

@@ -7,7 +7,7 @@ tail -1 $O/frames_parity.log
 for c in ${CONFIGS:-c3 c4}; do
   for v in ${MODES:-1 0}; do
     if [ "$v" = d ]; then unset AAA_FRAMES_FWD AAA_FRAMES_BWD; else export AAA_FRAMES_FWD=$v AAA_FRAMES_BWD=$v; fi
-    timeout -k 10 300 python bench.py --config $c --no-cpu-baseline --no-dropin --steps 10 > $O/fb_${c}_$v.json 2> $O/fb_${c}_$v.err || { echo "bench $c $v rc=$?"; tail $O/fb_${c}_$v.err; exit 1; }
+    timeout -k 10 300 python bench.py --full --config $c --no-cpu-baseline --no-dropin --steps 10 > $O/fb_${c}_$v.json 2> $O/fb_${c}_$v.err || { echo "bench $c $v rc=$?"; tail $O/fb_${c}_$v.err; exit 1; }
     python -c "import json;d=json.loads(open('$O/fb_${c}_$v.json').read().strip().splitlines()[-1]);print('$c frames=$v',d['value'],d['ms_per_step'],json.dumps(d['kernels']))"
   done
 done

@@ -7,11 +7,11 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/r05t; mkdir -p $O
 BA="--no-cpu-baseline --no-dropin --no-episode"
 for c in "${@:-c2}"; do
   cd $R
-  timeout -k 10 200 python bench.py --config $c $BA --timed-steps 20 > $O/${c}_plain20.json 2> $O/${c}_plain20.err || { echo "plain20 $c rc=$?"; exit 1; }
-  timeout -k 10 200 python bench.py --config $c $BA --timed-steps 1 > $O/${c}_plain1.json 2> $O/${c}_plain1.err || { echo "plain1 $c rc=$?"; exit 1; }
+  timeout -k 10 200 python bench.py --full --config $c $BA --timed-steps 20 > $O/${c}_plain20.json 2> $O/${c}_plain20.err || { echo "plain20 $c rc=$?"; exit 1; }
+  timeout -k 10 200 python bench.py --full --config $c $BA --timed-steps 1 > $O/${c}_plain1.json 2> $O/${c}_plain1.err || { echo "plain1 $c rc=$?"; exit 1; }
   cd /tmp && export TMPDIR=/tmp
   for k in 20 1; do
-    timeout -k 10 240 rocprofv3 --kernel-trace --stats -d $O/prof_${c}_$k -o run --output-format csv -- python $R/bench.py --config $c $BA --timed-steps $k > $O/${c}_prof$k.json 2> $O/${c}_prof$k.err || { echo "prof $c $k rc=$?"; exit 1; }
+    timeout -k 10 240 rocprofv3 --kernel-trace --stats -d $O/prof_${c}_$k -o run --output-format csv -- python $R/bench.py --full --config $c $BA --timed-steps $k > $O/${c}_prof$k.json 2> $O/${c}_prof$k.err || { echo "prof $c $k rc=$?"; exit 1; }
     python $R/tools/trace_vs_events.py $O/prof_${c}_$k/run_kernel_trace.csv $O/${c}_prof$k.json $k > $O/${c}_cmp$k.json || exit 1
   done
   for f in $O/${c}_plain20.json $O/${c}_plain1.json $O/${c}_prof20.json $O/${c}_prof1.json; do

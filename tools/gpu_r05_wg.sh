@@ -7,7 +7,7 @@ timeout -k 10 600 python -u -m pytest -x -v --timeout 200 --timeout-method threa
 BA="--no-cpu-baseline --no-dropin --no-episode"
 for i in 1 2; do
   for t in 4 6; do
-    AAA_WGRAD_S6_TILE=$t timeout -k 10 200 python bench.py $BA > $O/t${t}_$i.json 2> $O/t${t}_$i.err || { echo "t$t rc=$?"; tail $O/t${t}_$i.err; exit 1; }
+    AAA_WGRAD_S6_TILE=$t timeout -k 10 200 python bench.py --full $BA > $O/t${t}_$i.json 2> $O/t${t}_$i.err || { echo "t$t rc=$?"; tail $O/t${t}_$i.err; exit 1; }
   done
 done
 for f in $O/t*.json; do python -c "import json;d=json.loads(open('$f').read().strip().splitlines()[-1]);print('$f',d['value'],d['ms_per_step'],{k:v.get('avg_us') for k,v in d['kernels'].items() if 'avg_us' in v})"; done

@@ -13,7 +13,7 @@ tail -2 $O/tests.log; cp gpurun_out/kink_report.jsonl $O/ 2>/dev/null
 for c in c2 c3 c4; do
   for arm in base new; do
     lib=$R/tools/ablibs/libaaa_base.so; [ $arm = new ] && lib=$R/towards-interpretable-reinforcement-learning-using-attention-augmented-agents-replication_amd/libaaa.so
-    AAA_LIB=$lib timeout -k 10 300 python bench.py --config $c --no-cpu-baseline --no-dropin --no-episode > $O/${c}_$arm.json 2> $O/${c}_$arm.err || { echo "bench $c $arm rc=$?"; tail $O/${c}_$arm.err; exit 1; }
+    AAA_LIB=$lib timeout -k 10 300 python bench.py --full --config $c --no-cpu-baseline --no-dropin --no-episode > $O/${c}_$arm.json 2> $O/${c}_$arm.err || { echo "bench $c $arm rc=$?"; tail $O/${c}_$arm.err; exit 1; }
     python -c "import json;d=json.loads(open('$O/${c}_$arm.json').read().strip().splitlines()[-1]);print('$c $arm',d['value'],d['ms_per_step'],[(n[:22],v.get('avg_us',v.get('ms'))) for n,v in d['kernels'].items()][:3])"
   done
 done

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/r06ab2; mkdir -p $O; cd $R; export
 B=$R/tools/ablibs/libaaa_base.so
 run() {  # name config env...
   local n=$1 c=$2; shift 2
-  env "$@" timeout -k 10 300 python bench.py --config $c --no-cpu-baseline --no-dropin --no-episode > $O/$n.json 2> $O/$n.err || { echo "bench $n rc=$?"; tail -3 $O/$n.err; exit 1; }
+  env "$@" timeout -k 10 300 python bench.py --full --config $c --no-cpu-baseline --no-dropin --no-episode > $O/$n.json 2> $O/$n.err || { echo "bench $n rc=$?"; tail -3 $O/$n.err; exit 1; }
   python -c "
 import json;d=json.loads(open('$O/$n.json').read().strip().splitlines()[-1]);k=d['kernels']
 print('$n',d['value'],d['ms_per_step'],'fwd',k['ConvLSTM forward step']['avg_us'],'bptt',k['ConvLSTM BPTT step']['avg_us'])"

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/r06bwl; mkdir -p $O; cd $R; export
 B=$R/tools/ablibs/libaaa_base.so
 run() {  # name, env...
   local n=$1; shift
-  env "$@" timeout -k 10 300 python bench.py --config ${CFG:-c3} --no-cpu-baseline --no-dropin --no-episode > $O/$n.json 2> $O/$n.err || { echo "bench $n rc=$?"; tail -3 $O/$n.err; exit 1; }
+  env "$@" timeout -k 10 300 python bench.py --full --config ${CFG:-c3} --no-cpu-baseline --no-dropin --no-episode > $O/$n.json 2> $O/$n.err || { echo "bench $n rc=$?"; tail -3 $O/$n.err; exit 1; }
   python -c "import json;d=json.loads(open('$O/$n.json').read().strip().splitlines()[-1]);k=d['kernels']['ConvLSTM BPTT step'];print('$n',d['value'],d['ms_per_step'],k['avg_us'],k['frac'])"
 }
 run base AAA_LIB=$B

@@ -7,12 +7,12 @@ timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smok
 tail -1 $O/smoke.log
 timeout -k 10 900 python -u -m pytest -x -q --timeout 200 --timeout-method thread -m gpu tests > $O/tests.log 2>&1; rc=$?
 tail -2 $O/tests.log; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 600 python bench.py > $O/c2_bench.json 2> $O/c2_bench.err || { echo "c2 rc=$?"; tail -5 $O/c2_bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $O/c2_bench.json 2> $O/c2_bench.err || { echo "c2 rc=$?"; tail -5 $O/c2_bench.err; exit 1; }
 for c in c3 c4 c5; do
-  timeout -k 10 300 python bench.py --config $c --no-cpu-baseline --no-episode > $O/${c}_bench.json 2> $O/${c}_bench.err || { echo "$c rc=$?"; tail -5 $O/${c}_bench.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --config $c --no-cpu-baseline --no-episode > $O/${c}_bench.json 2> $O/${c}_bench.err || { echo "$c rc=$?"; tail -5 $O/${c}_bench.err; exit 1; }
 done
 cd /tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof_c2 -o run --output-format csv -- python $R/bench.py --no-cpu-baseline --no-dropin --no-episode > $O/c2_prof.json 2> $O/c2_prof.err || { echo "prof rc=$?"; exit 1; }
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof_c2 -o run --output-format csv -- python $R/bench.py --full --no-cpu-baseline --no-dropin --no-episode > $O/c2_prof.json 2> $O/c2_prof.err || { echo "prof rc=$?"; exit 1; }
 python $R/tools/trace_vs_events.py $O/prof_c2/run_kernel_trace.csv $O/c2_prof.json 1 > $O/c2_cmp.json || exit 1
 for c in c2 c3 c4 c5; do python -c "
 import json;d=json.loads(open('$O/${c}_bench.json').read().strip().splitlines()[-1])

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/r06stag; mkdir -p $O; cd $R
 A=$R/towards-interpretable-reinforcement-learning-using-attention-augmented-agents-replication_amd/libaaa_ablation.so
 run() {  # name, env...
   local n=$1; shift
-  env AAA_LIB=$A "$@" timeout -k 10 300 python bench.py --config c3 --steps 10 --no-cpu-baseline --no-dropin --no-episode > $O/$n.json 2> $O/$n.err || { echo "bench $n rc=$?"; tail -3 $O/$n.err; exit 1; }
+  env AAA_LIB=$A "$@" timeout -k 10 300 python bench.py --full --config c3 --steps 10 --no-cpu-baseline --no-dropin --no-episode > $O/$n.json 2> $O/$n.err || { echo "bench $n rc=$?"; tail -3 $O/$n.err; exit 1; }
   python -c "import json;d=json.loads(open('$O/$n.json').read().strip().splitlines()[-1]);k=d['kernels']['ConvLSTM BPTT step'];print('$n',d['value'],k['avg_us'])"
 }
 run base

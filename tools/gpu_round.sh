@@ -9,6 +9,6 @@ step() { local name=$1; shift; "$@"; local rc=$?; echo "$name rc=$rc" >&3; if [ 
 exec 3>&1
 step parity timeout -k 10 700 python -m pytest tests -q -m gpu -x -p no:cacheprovider > $O/parity.log 2>&1
 step smoke timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
-step bench timeout -k 10 400 python bench.py ${BENCH_ARGS} > $O/bench.json 2> $O/bench.err
+step bench timeout -k 10 400 python bench.py --full ${BENCH_ARGS} > $O/bench.json 2> $O/bench.err
 cd /tmp && export TMPDIR=/tmp
 step prof timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline ${BENCH_ARGS} > $O/prof.log 2>&1

@@ -2,7 +2,7 @@
 the SAME process.
 
   rocprofv3 --kernel-trace --stats -d D -o run --output-format csv -- \
-      python bench.py --timed-steps K ... > bench.json
+      python bench.py --full --timed-steps K ... > bench.json
   python tools/trace_vs_events.py D/run_kernel_trace.csv bench.json K
 
 For every MFMA timer class of the bench line (forward recurrence, BPTT,
