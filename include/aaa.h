@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define AAA_ABI_VERSION 9
+#define AAA_ABI_VERSION 10
 
 enum aaa_status {
   AAA_OK = 0,
@@ -476,6 +476,33 @@ int aaa_attn_fwd(int F, int h, int w, int nq, const float* O, const float* S, co
  * frame (logits path + the answer's Q columns; sum over F for a shared Q). */
 int aaa_attn_bwd(int F, int h, int w, int nq, const float* O, const float* S, const float* Q, int q_stride,
                  const float* attn, const float* danswer, float* dO, float* dQ, hipStream_t stream);
+/* The same readout on bf16 O, as the bf16 learner runs it (ABI 10): O is bf16,
+ * frame rows of h*w positions at a pitch of o_ld elements (the learner reads
+ * the h half of its [x | h] rows: pitch 192, pointer 64 elements into the
+ * row).  o_ld must be >= 136 and a multiple of 8 (16-byte loads; the last
+ * piece a row's load touches reaches 8 elements past the 128 channels, read
+ * and not used, so the buffer must extend that far past the last row).
+ * sq_scratch (h*w*nq floats, 16-byte aligned) may be set only with q_stride
+ * 0: the entry first fills it with the constant query's basis logits
+ * S.Q[:, 8:] and the kernels take them from there (the learner's call); NULL:
+ * the kernels compute the basis logits per frame (the stateful core's call).
+ * Arguments are checked before the device, so a refusal needs no GPU.
+ * AAA_ATTN_MFMA (default 1: the readout product on the MFMA; 0: the VALU
+ * kernel) is read on every call. */
+int aaa_attn_fwd_bf16(int F, int h, int w, int nq, const void* O, int o_ld, const float* S, const float* Q,
+                      int q_stride, float* sq_scratch, const float* prev_reward, const float* prev_action,
+                      float* attn, float* answer, hipStream_t stream);
+/* Its backward.  danswer rows have a pitch of da_ld floats (>= the columns
+ * read: the nq*184 readout columns, plus the nq*72 Q columns with add_q);
+ * add_q != 0 adds the answer row's Q columns into dQ (the stateful core; the
+ * learner passes 0 and adds them downstream).  dO_quad_major != 0 writes dO
+ * in the frame-resident BPTT's layout: the frame's value for position p,
+ * channels 4k..4k+3, at float offset (k*h*w + p)*4 of the frame's h*w*128
+ * floats.  AAA_ATTN_BWD_MFMA (default 1: the dA pass on the MFMA above 256
+ * grid positions; 2: everywhere; 0: never) is read on every call. */
+int aaa_attn_bwd_bf16(int F, int h, int w, int nq, const void* O, int o_ld, const float* S, const float* Q,
+                      int q_stride, const float* attn, const float* danswer, int da_ld, int add_q,
+                      int dO_quad_major, float* dO, float* dQ, hipStream_t stream);
 
 /* ---- index-arithmetic self-checks (host only, no device needed) ----
  * Every pixel / tap / tile index in the kernels is divided by a runtime

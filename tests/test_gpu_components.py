@@ -225,7 +225,10 @@ def test_agent_state_is_reference_layout(cuda):
 
 
 # ------------------------------------------------------------- attention ----
-@pytest.mark.parametrize("nq,hw", [(4, (11, 11)), (8, (21, 21)), (4, (27, 20))])
+# the edge grids of tests/attn_bf16_ref.py too: the fp32 VALU kernels have the same two-positions-per-lane
+# switch at P > 256, the same prefetch switch and the same LDS sizing
+@pytest.mark.parametrize("nq,hw", [(4, (11, 11)), (8, (21, 21)), (4, (27, 20)),
+                                   (4, (3, 5)), (8, (8, 8)), (4, (16, 16)), (8, (17, 16)), (8, (16, 32)), (4, (19, 27))])
 @pytest.mark.parametrize("per_frame_q", [False, True])
 def test_attention_readout_fwd_bwd_vs_oracle(cuda, nq, hw, per_frame_q):
     h, w = hw

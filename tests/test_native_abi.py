@@ -33,7 +33,7 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_abi_version():
-    assert N.load().aaa_abi_version() == N.ABI_VERSION == 9
+    assert N.load().aaa_abi_version() == N.ABI_VERSION == 10
 
 
 @pytest.mark.parametrize("H,W,hw", [(84, 84, (11, 11)), (168, 168, (21, 21)), (210, 160, (27, 20))])
@@ -168,6 +168,34 @@ def test_adam_counted_rejects_null_counter():
     lib = N.load()
     hp = N.AdamHP(1e-3, 0.9, 0.999, 1e-8, 0.0, 0, 0)
     assert lib.aaa_adam_step_counted(ctypes.byref(hp), None, None, 0, None, None, None, None, None, None, None) == -1
+
+
+@pytest.mark.parametrize("what,nq,o_ld,q_stride,sq,word", [
+    ("o_ld below the 136 the 16-byte loads need", 4, 128, 0, None, b"o_ld"),
+    ("o_ld not a multiple of 8", 4, 140, 0, None, b"o_ld"),
+    ("sq_scratch with a per-frame query", 4, 192, 4 * 72, 16, b"sq_scratch"),
+    ("nq = 5", 5, 192, 0, None, b"nq"),
+])
+def test_attn_bf16_rejects_bad_args_without_gpu(what, nq, o_ld, q_stride, sq, word):
+    """aaa_attn_fwd_bf16 / aaa_attn_bwd_bf16 check their arguments before the
+    device: each refusal returns AAA_E_ARG (-1) with a message on a CPU-only box."""
+    lib = N.load()
+    rc = lib.aaa_attn_fwd_bf16(3, 11, 11, nq, 16, o_ld, 16, 16, q_stride, sq, None, None, 16, 16, None)
+    assert rc == -1, what
+    assert word in lib.aaa_last_error(), lib.aaa_last_error()
+    if sq is None:   # (the backward has no sq_scratch)
+        rc = lib.aaa_attn_bwd_bf16(3, 11, 11, nq, 16, o_ld, 16, 16, q_stride, 16, 16, nq * 184, 0, 0, 16, 16, None)
+        assert rc == -1, what
+        assert word in lib.aaa_last_error(), lib.aaa_last_error()
+
+
+def test_attn_bwd_bf16_rejects_short_danswer_pitch_without_gpu():
+    """da_ld must cover the columns read: nq*184, plus the nq*72 Q columns with add_q."""
+    lib = N.load()
+    assert lib.aaa_attn_bwd_bf16(3, 11, 11, 4, 16, 192, 16, 16, 0, 16, 16, 4 * 184 - 1, 0, 0, 16, 16, None) == -1
+    assert b"da_ld" in lib.aaa_last_error()
+    assert lib.aaa_attn_bwd_bf16(3, 11, 11, 4, 16, 192, 16, 16, 0, 16, 16, 4 * 184, 1, 0, 16, 16, None) == -1
+    assert b"da_ld" in lib.aaa_last_error()
 
 
 def test_package_modules_import():

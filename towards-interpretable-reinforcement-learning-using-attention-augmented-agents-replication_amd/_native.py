@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AAA_LIB") or os.path.join(_HERE, "libaaa.so")
 
 F32, BF16 = 0, 1
-ABI_VERSION = 9   # include/aaa.h AAA_ABI_VERSION
+ABI_VERSION = 10  # include/aaa.h AAA_ABI_VERSION
 E_STRANDED = -5   # AAA_E_STRANDED
 BWD_HEAD, BWD_CORE, BWD_VISION, BWD_ALL = 1, 2, 4, 7
 FWD_VISION, FWD_CORE, FWD_TAIL, FWD_ALL = 1, 2, 4, 7
@@ -28,7 +28,7 @@ EXPORTS = (
     "aaa_adam_step", "aaa_reinforce", "aaa_sample_actions", "aaa_fastdiv_check", "aaa_divisor_log",
     "aaa_convlstm_packed_bytes", "aaa_convlstm_workspace_bytes", "aaa_convlstm_pack", "aaa_convlstm_cell_fwd",
     "aaa_convlstm_cell_bwd", "aaa_vision_cnn_packed_bytes", "aaa_vision_cnn_workspace_bytes", "aaa_vision_cnn_pack",
-    "aaa_vision_cnn_fwd", "aaa_vision_cnn_bwd", "aaa_attn_fwd", "aaa_attn_bwd",
+    "aaa_vision_cnn_fwd", "aaa_vision_cnn_bwd", "aaa_attn_fwd", "aaa_attn_bwd", "aaa_attn_fwd_bf16", "aaa_attn_bwd_bf16",
     "aaa_actor_workspace_bytes", "aaa_actor_step", "aaa_pair_status", "aaa_pair_flag", "aaa_pair_flag_at",
     "aaa_adam_step_guarded", "aaa_adam_step_counted", "aaa_workspace_region",
     "aaa_core_elem_bytes", "aaa_forward_phases", "aaa_core_export", "aaa_core_import",
@@ -158,6 +158,8 @@ def load(path: str = LIB_PATH):
             "aaa_vision_cnn_bwd": (I, [ctypes.POINTER(CnnDesc), P, P, P, P, P, P]),
             "aaa_attn_fwd": (I, [I, I, I, I, P, P, P, I, P, P, P, P, P]),
             "aaa_attn_bwd": (I, [I, I, I, I, P, P, P, I, P, P, P, P, P]),
+            "aaa_attn_fwd_bf16": (I, [I, I, I, I, P, I, P, P, I, P, P, P, P, P, P]),
+            "aaa_attn_bwd_bf16": (I, [I, I, I, I, P, I, P, P, I, P, P, I, I, I, P, P, P]),
             "aaa_fastdiv_check": (I, [ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.POINTER(ctypes.c_ulonglong)]),
             "aaa_divisor_log": (I, [I, ctypes.POINTER(ctypes.c_uint), I]),
             "aaa_actor_workspace_bytes": (S, [CP]),

@@ -5,11 +5,19 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <cstdlib>
 #include <type_traits>
 #include <mutex>
 #include <vector>
 
 namespace aaa {
+
+// A path selector read from the environment on every call: the
+// parity tests switch paths inside one process.
+inline int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));

@@ -1166,7 +1166,8 @@ hipError_t attn_fwd(OSrc O, const float* S, const float* Q, const float* SQ, con
   constexpr int pre_env = -1, sl_env = -1;
 #endif
   // the readout product on the MFMA for bf16 O (attn_mfma.h); AAA_ATTN_MFMA=0: the VALU kernel below
-  static const int mfma_env = getenv("AAA_ATTN_MFMA") ? atoi(getenv("AAA_ATTN_MFMA")) : 1;
+  // (read on every call: tests/test_gpu_attn_bf16.py runs both in one process)
+  const int mfma_env = env_int("AAA_ATTN_MFMA", 1);
   if (mfma_env && O.bf16 && (nq == 4 || nq == 8)) {
     if (O.ld < 128 || O.ld % 8) return hipErrorInvalidValue;   // 16-B loads
     const size_t sh = attn_mfma_lds(P, nq);
@@ -1253,8 +1254,8 @@ hipError_t attn_bwd(OSrc O, const float* S, const float* Q, const float* Am, con
   if (ppl != 1 && ppl != 2) return hipErrorInvalidValue;
   // bf16 O on large grids: the dA pass on the MFMA (attn_mfma.h; C5, P = 441: 320 -> 290 us; at 84x84,
   // P = 121, the VALU pass is faster: 126 vs 139 us, profiles/r06/ab/attn_bwd_mfma/).  AAA_ATTN_BWD_MFMA=0:
-  // the VALU kernel everywhere, 2: the MFMA pass everywhere
-  static const int bm_env = getenv("AAA_ATTN_BWD_MFMA") ? atoi(getenv("AAA_ATTN_BWD_MFMA")) : 1;
+  // the VALU kernel everywhere, 2: the MFMA pass everywhere (read on every call, as AAA_ATTN_MFMA)
+  const int bm_env = env_int("AAA_ATTN_BWD_MFMA", 1);
   if (O.bf16 && (bm_env == 2 || (bm_env == 1 && P > 256))) {
     const __bf16* o = (const __bf16*)O.p;
     nq == 4 ? launch(k_attn_bwd_mfma<4>, o) : launch(k_attn_bwd_mfma<8>, o);

@@ -214,10 +214,7 @@ template <typename T> using CfgSFor = std::conditional_t<std::is_same<T, float>:
 //   (forward 4 = 128x64 8 waves, 5 = 32x64 split-K, 6 = 64x64 BK64; BPTT 4 = 32x64 BK128
 //   4-way, 5 = BK64 4-way, 6 = 64x64, 9 = 64x32 BK128 4-way).  The default picks by how many 32x32
 //   output tiles the step has, i.e. how many waves it can feed; measured on C2.
-inline int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
+// (env_int: common.h)
 // A/B-only knobs (the same-box comparisons of tools/gpu_ab*.sh): read from the
 // environment only in -DAAA_ABLATION builds (make ablation -> libaaa_ablation.so,
 // loaded through AAA_LIB); the product library takes the default.  env_int stays

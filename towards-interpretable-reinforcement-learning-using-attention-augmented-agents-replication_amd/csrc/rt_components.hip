@@ -436,12 +436,28 @@ int aaa_vision_cnn_bwd(const aaa_cnn_desc* d, const void* packed, const float* d
              : cnn_bwd_impl<float>(C, (const char*)packed, dy2, dy1, cnn_grads, (char*)workspace, stream);
 }
 
-static int check_attn(int F, int h, int w, int nq, int q_stride) {
+static int check_attn_args(int F, int h, int w, int nq, int q_stride) {
   if (F < 1 || h < 1 || w < 1) return fail(AAA_E_ARG, "attn: need F, h, w >= 1");
   if (nq != 4 && nq != 8) return fail(AAA_E_ARG, "attn: nq must be 4 or 8 (got %d)", nq);
   if (q_stride != 0 && q_stride != nq * 72) return fail(AAA_E_ARG, "attn: q_stride must be 0 or nq*72");
   if ((size_t)F * h * w * 128 >= (size_t(1) << 31)) return fail(AAA_E_ARG, "attn: F*h*w too large; split F");
-  return check_device();
+  return AAA_OK;
+}
+
+static int check_attn(int F, int h, int w, int nq, int q_stride) {
+  const int r = check_attn_args(F, h, w, nq, q_stride);
+  return r ? r : check_device();
+}
+
+// bf16 O rows at pitch o_ld: the launchers' rules (16-B loads; the VALU kernels' last piece of a row
+// reaches 8 elements past the 128 channels), checked here so that the refusal needs no device
+static int check_attn_bf16(int F, int h, int w, int nq, int q_stride, int o_ld) {
+  const int r = check_attn_args(F, h, w, nq, q_stride);
+  if (r) return r;
+  if (o_ld < 136 || o_ld % 8)
+    return fail(AAA_E_ARG, "attn: bf16 O needs a row pitch o_ld >= 136 and a multiple of 8 (got %d)", o_ld);
+  if ((size_t)h * w * o_ld * 2 >= (size_t(1) << 31)) return fail(AAA_E_ARG, "attn: h*w*o_ld too large");
+  return AAA_OK;
 }
 
 int aaa_attn_fwd(int F, int h, int w, int nq, const float* O, const float* S, const float* Q, int q_stride,
@@ -465,6 +481,45 @@ int aaa_attn_bwd(int F, int h, int w, int nq, const float* O, const float* S, co
   if (!aligned16(O) || !aligned16(S) || !aligned16(dO)) return fail(AAA_E_ALIGN, "O, S, dO must be 16-byte aligned");
   TimerScope tim(AAA_TIMER_ATTN_BWD, stream, (double)F * attn_bwd_bytes(h * w, nq), "k_attn_bwd (aaa_attn_bwd)");
   HIPCHK(attn_bwd(o_f32(O), S, Q, attn, danswer, 256 * nq + 2, F, h * w, nq, dO, dQ, stream, q_stride, 1));
+  return AAA_OK;
+}
+
+int aaa_attn_fwd_bf16(int F, int h, int w, int nq, const void* O, int o_ld, const float* S, const float* Q,
+                      int q_stride, float* sq_scratch, const float* prev_reward, const float* prev_action,
+                      float* attn, float* answer, hipStream_t stream) {
+  int r = check_attn_bf16(F, h, w, nq, q_stride, o_ld);
+  if (r) return r;
+  if (sq_scratch && q_stride != 0)
+    return fail(AAA_E_ARG, "attn_fwd_bf16: sq_scratch (the constant query's basis logits) needs q_stride 0");
+  if (!O || !S || !Q || !attn || !answer) return fail(AAA_E_ARG, "attn_fwd_bf16: O/S/Q/attn/answer must be set");
+  if (!aligned16(O) || !aligned16(S) || (sq_scratch && !aligned16(sq_scratch)))
+    return fail(AAA_E_ALIGN, "O, S and sq_scratch must be 16-byte aligned");
+  if ((r = check_device())) return r;
+  const int P = h * w;
+  if (sq_scratch) HIPCHK(query_sq(S, Q, P, nq, sq_scratch, stream));
+  TimerScope tim(AAA_TIMER_ATTN_FWD, stream, (double)F * attn_fwd_bytes(P, nq, 256 * nq + 2, 2),
+                 "attention readout forward, bf16 O (aaa_attn_fwd_bf16)");
+  HIPCHK(attn_fwd(o_bf16((const __bf16*)O, o_ld), S, Q, sq_scratch, prev_reward, prev_action, F, P, nq, attn, answer,
+                  256 * nq + 2, stream, q_stride));
+  return AAA_OK;
+}
+
+int aaa_attn_bwd_bf16(int F, int h, int w, int nq, const void* O, int o_ld, const float* S, const float* Q,
+                      int q_stride, const float* attn, const float* danswer, int da_ld, int add_q,
+                      int dO_quad_major, float* dO, float* dQ, hipStream_t stream) {
+  int r = check_attn_bf16(F, h, w, nq, q_stride, o_ld);
+  if (r) return r;
+  const int da_cols = nq * 184 + (add_q ? nq * 72 : 0);   // the readout columns, and Q's copy when it is added
+  if (da_ld < da_cols)
+    return fail(AAA_E_ARG, "attn_bwd_bf16: da_ld %d is below the %d danswer columns read", da_ld, da_cols);
+  if (!O || !S || !Q || !attn || !danswer || !dO || !dQ)
+    return fail(AAA_E_ARG, "attn_bwd_bf16: O/S/Q/attn/danswer/dO/dQ must be set");
+  if (!aligned16(O) || !aligned16(S) || !aligned16(dO)) return fail(AAA_E_ALIGN, "O, S, dO must be 16-byte aligned");
+  if ((r = check_device())) return r;
+  TimerScope tim(AAA_TIMER_ATTN_BWD, stream, (double)F * attn_bwd_bytes(h * w, nq, 2),
+                 "attention readout backward, bf16 O (aaa_attn_bwd_bf16)");
+  HIPCHK(attn_bwd(o_bf16((const __bf16*)O, o_ld), S, Q, attn, danswer, da_ld, F, h * w, nq, dO, dQ, stream, q_stride,
+                  add_q ? 1 : 0, dO_quad_major ? 1 : 0));
   return AAA_OK;
 }
 
