@@ -441,6 +441,23 @@ struct GemmCfgS3L : GemmCfg<float, BI_, BJ_, BK_, WI_, WJ_, 1> {
   static constexpr bool SPLIT3 = true, SPLIT6L = true, TWO_PARTS = true;
   static constexpr int FD = FD_;
 };
+// GemmCfgS6L whose K loop runs whole pairs of tiles, with an odd last tile after it.  With
+// ``if (kt + 1 < nk) step(odd)`` inside the loop, the loop keeps an edge from the even step back to
+// its own header (never taken: kt + 1 >= nk ends the loop), and the waits for the global loads are
+// placed for that edge too: every even step began by waiting for the loads of tile kt+1, issued one
+// step before, instead of keeping them in flight to their commit (FD 2 held for the odd steps only).
+// CI_ = 1: the commit of tile kt+1 sits in the MFMAs' basic block and is issued among them (three
+// VALU instructions after each MFMA from the 13th on), instead of after the last MFMA with the matrix
+// pipe idle.  For that it is unconditional: past the last tile it fills the LDS stage nobody reads again.
+template <int BI_, int BJ_, int BK_, int WI_, int WJ_, int FD_ = 2, int CI_ = 1>
+struct GemmCfgS6LK : GemmCfgS6L<BI_, BJ_, BK_, WI_, WJ_, FD_> {
+  static constexpr bool KPAIRS = true;
+  static constexpr bool COMMIT_ILV = CI_ != 0;
+};
+template <class C, class = void> struct kpairs_of : std::false_type {};
+template <class C> struct kpairs_of<C, std::enable_if_t<C::KPAIRS>> : std::true_type {};
+template <class C, class = void> struct commit_ilv_of : std::false_type {};
+template <class C> struct commit_ilv_of<C, std::enable_if_t<C::KPAIRS>> : std::integral_constant<bool, C::COMMIT_ILV> {};
 template <class C, class = void> struct two_parts_of : std::false_type {};
 template <class C> struct two_parts_of<C, std::enable_if_t<C::TWO_PARTS>> : std::true_type {};
 // 4 fp32 of a staged chunk -> hi, lo bf16 parts (split_bf16), 8 B each, ``plane`` elements apart
@@ -747,7 +764,7 @@ gemm_kernel_s6l(typename LA::Params pa, typename LB::Params pb, EP ep, int K, in
   la.fetch(kb, ke, ra[0]);
   lb.fetch(kb, ke, rb[0]);
   if constexpr (FD == 2) {
-    if (nk > 1) {
+    if (nk > 1 || commit_ilv_of<C>::value) {   // (the unconditional commit reads the stage)
       la.fetch(kb + BK, ke, ra[1]);
       lb.fetch(kb + BK, ke, rb[1]);
     }
@@ -773,6 +790,7 @@ gemm_kernel_s6l(typename LA::Params pa, typename LB::Params pb, EP ep, int K, in
       la.fetch(kb + (kt + 1) * BK, ke, ra[0]);
       lb.fetch(kb + (kt + 1) * BK, ke, rb[0]);
     }
+    constexpr int rs1 = FD == 2 ? (e ^ 1) : 0;   // tile kt+1: register stage e ^ 1 (FD 2) or 0
 #pragma unroll
     for (int s2 = 0; s2 < BK / 16; ++s2) {
       const int kofs = 16 * s2 + 8 * h;
@@ -810,12 +828,209 @@ gemm_kernel_s6l(typename LA::Params pa, typename LB::Params pb, EP ep, int K, in
           acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[a][0], bfr[b][0], acc[a][b], 0, 0, 0);
         }
     }
-    if (more) {   // tile kt+1: register stage e ^ 1 (FD 2) or 0
-      constexpr int rs1 = FD == 2 ? (e ^ 1) : 0;
+    if constexpr (commit_ilv_of<C>::value) {
+      // the first 12 MFMAs alone: the loads of tile kt+1 keep that long to land
+      commit_a(nxt, ra[rs1]);
+      commit_b(nxt + NPT * PA, rb[rs1]);
+      __builtin_amdgcn_sched_group_barrier(0x8, 12, 0);
+#pragma unroll
+      for (int i = 0; i < 6 * MI * MJ * (BK / 16) - 12; ++i) {
+        __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);   // one MFMA,
+        __builtin_amdgcn_sched_group_barrier(0x2, 3, 0);   // three VALU
+      }
+    } else if (more) {
       commit_a(nxt, ra[rs1]);
       commit_b(nxt + NPT * PA, rb[rs1]);
     }
     __syncthreads();
+  };
+  if constexpr (kpairs_of<C>::value) {
+    for (int kt = 0; kt + 1 < nk; kt += 2) {
+      step(kt, std::integral_constant<int, 0>{});
+      step(kt + 1, std::integral_constant<int, 1>{});
+    }
+    if (nk & 1) step(nk - 1, std::integral_constant<int, 0>{});
+  } else
+  for (int kt = 0; kt < nk; kt += 2) {
+    step(kt, std::integral_constant<int, 0>{});
+    if (kt + 1 < nk) step(kt + 1, std::integral_constant<int, 1>{});
+  }
+#pragma unroll
+  for (int a = 0; a < MI; ++a)
+#pragma unroll
+    for (int b = 0; b < MJ; ++b)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int i = i0 + wi * WTI + a * 32 + 8 * g + 4 * h;
+        const int j = j0 + wj * WTJ + b * 32 + r32;
+        ep(i, j, acc[a][b][4 * g], acc[a][b][4 * g + 1], acc[a][b][4 * g + 2], acc[a][b][4 * g + 3]);
+      }
+}
+
+// configs gemm_kernel_s6p takes: three-part split-at-commit tiles of 8 waves with two register stages
+template <class C, class = void> struct s6p_of : std::false_type {};
+template <class C>
+struct s6p_of<C, std::enable_if_t<C::SPLIT6L && C::SPLIT6 && C::FD == 2 && C::WI * C::WJ == 8>>
+    : std::integral_constant<bool, !bexact_of<C>::value> {};
+
+// Paired-segment form of gemm_kernel_s6l (three-part configs, FD 2, 8 waves): the waves split
+// into two halves, waves 0..3 and 4..7, one wave of each half per SIMD.  A K tile takes two
+// segments, each ended by a workgroup barrier: in the first, half 0 reads its fragments of tile kt
+// and issues its MFMAs while half 1 commits its chunks of tile kt+1 to the other LDS stage and
+// issues its global loads; in the second the roles swap.  So a SIMD's matrix pipe always has one
+// wave in its MFMA segment, instead of two waves that read, multiply and commit in the same
+// phase.  After the second barrier tile kt+1 is complete and tile kt's stage is free (both
+// halves have multiplied it): the two LDS stages of gemm_kernel_s6l suffice.  Every accumulator
+// receives the products of gemm_kernel_s6l in its order: a workgroup's partial tile is
+// bit-identical.  V (A/B, tools/ubench/wgrad_s6l_ablate.hip): 1 = s_setprio(1) for half 1,
+// 2 = the A fragments read one 32-row group ahead of their MFMAs instead of all at the top,
+// 4 = the loads of tile kt+2 issued before the commit (one tile in flight) instead of those of
+// tile kt+3 after it (two).  Slower than gemm_kernel_s6l in every variant (C2 643 us at V = 5, the
+// best, against 603: each half's fragment reads are exposed in its own segment, and a SIMD's matrix
+// pipe has one wave to issue from): ablation builds only.
+template <class C, class LA, class LB, class EP, int V = 5>
+__global__ void __launch_bounds__(C::NT)
+gemm_kernel_s6p(typename LA::Params pa, typename LB::Params pb, EP ep, int K, int kchunk, TileMap tm) {
+  constexpr int BI = C::BI, BJ = C::BJ, BK = C::BK, WI = C::WI, WJ = C::WJ;
+  constexpr int WTI = BI / WI, WTJ = BJ / WJ, MI = WTI / 32, MJ = WTJ / 32;
+  static_assert(C::WK == 1 && MI >= 1 && MJ >= 1 && BK % 16 == 0, "tile shape");
+  static_assert(C::FD == 2 && !two_parts_of<C>::value && !bexact_of<C>::value, "three-part FD 2 configs");
+  static_assert(WI * WJ == 8, "two halves of four waves: one wave of each half per SIMD");
+  using TA = TileK<__bf16, BI, BK, LA::KC>;
+  using TB = TileK<__bf16, BJ, BK, LB::KC>;
+  constexpr int PA = TA::ELEMS, PB = TB::ELEMS, STG = 3 * (PA + PB);
+  __shared__ __attribute__((aligned(16))) __bf16 smem[2 * STG];
+
+  int ti, tj, tz;
+  tile_of(tm, ti, tj, tz);
+  const int i0 = ti * BI, j0 = tj * BJ;
+  const int kb = tz * kchunk;
+  const int ke = min(K, kb + kchunk);
+  if (kb >= ke) return;
+
+  LA la(pa, i0);
+  LB lb(pb, j0);
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wi = wave / WJ, wj = wave - (wave / WJ) * WJ;
+  const int r32 = lane & 31, h = lane >> 5;
+  const bool half1 = wave >= 4;   // wave-uniform: the role branches below are scalar
+  if constexpr (V & 1) {
+    if (half1) __builtin_amdgcn_s_setprio(1);
+  }
+
+  f32x16 acc[MI][MJ];
+#pragma unroll
+  for (int a = 0; a < MI; ++a)
+#pragma unroll
+    for (int b = 0; b < MJ; ++b)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
+
+  const int nk = (ke - kb + BK - 1) / BK;
+  // register stage of tile t: t & 1.  Fetches past the slice are unconditional as in
+  // gemm_kernel_s6l (read in range or as zeros, never committed).
+  typename LA::Regs ra[2];
+  typename LB::Regs rb[2];
+  la.fetch(kb, ke, ra[0]);
+  lb.fetch(kb, ke, rb[0]);
+  la.fetch(kb + BK, ke, ra[1]);
+  lb.fetch(kb + BK, ke, rb[1]);
+  la.commit3(smem, PA, ra[0]);
+  lb.commit3(smem + 3 * PA, PB, rb[0]);
+  if constexpr (!(V & 4)) {
+    la.fetch(kb + 2 * BK, ke, ra[0]);
+    lb.fetch(kb + 2 * BK, ke, rb[0]);
+  }
+  __syncthreads();
+
+  // the MFMA segment of one tile: gemm_kernel_s6l's fragments and product order
+  auto mma = [&](const __bf16* cur) {
+    auto fa = [&](int a, int p, int kofs) { return frag_bf16<TA>(cur + p * PA, wi * WTI + a * 32 + r32, kofs); };
+    auto fb = [&](int b, int p, int kofs) {
+      return frag_bf16<TB>(cur + 3 * PA + p * PB, wj * WTJ + b * 32 + r32, kofs);
+    };
+    auto six = [&](f32x16& d, const bf16x8 (&x)[3], const bf16x8 (&y)[3]) {   // smallest products first
+      d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[2], y[0], d, 0, 0, 0);
+      d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[0], y[2], d, 0, 0, 0);
+      d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[1], y[1], d, 0, 0, 0);
+      d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[1], y[0], d, 0, 0, 0);
+      d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[0], y[1], d, 0, 0, 0);
+      d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[0], y[0], d, 0, 0, 0);
+    };
+#pragma unroll
+    for (int s2 = 0; s2 < BK / 16; ++s2) {
+      const int kofs = 16 * s2 + 8 * h;
+      bf16x8 bfr[MJ][3];
+      if constexpr (V & 2) {
+        bf16x8 af[2][3];
+#pragma unroll
+        for (int p = 0; p < 3; ++p) af[0][p] = fa(0, p, kofs);
+#pragma unroll
+        for (int b = 0; b < MJ; ++b)
+#pragma unroll
+          for (int p = 0; p < 3; ++p) bfr[b][p] = fb(b, p, kofs);
+#pragma unroll
+        for (int a = 0; a < MI; ++a) {
+          if (a + 1 < MI) {
+#pragma unroll
+            for (int p = 0; p < 3; ++p) af[(a + 1) & 1][p] = fa(a + 1, p, kofs);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int b = 0; b < MJ; ++b) six(acc[a][b], af[a & 1], bfr[b]);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      } else {
+        bf16x8 af[MI][3];
+#pragma unroll
+        for (int a = 0; a < MI; ++a)
+#pragma unroll
+          for (int p = 0; p < 3; ++p) af[a][p] = fa(a, p, kofs);
+#pragma unroll
+        for (int b = 0; b < MJ; ++b)
+#pragma unroll
+          for (int p = 0; p < 3; ++p) bfr[b][p] = fb(b, p, kofs);
+#pragma unroll
+        for (int a = 0; a < MI; ++a)
+#pragma unroll
+          for (int b = 0; b < MJ; ++b) six(acc[a][b], af[a], bfr[b]);
+      }
+    }
+  };
+  // the commit segment at tile kt (E = kt & 1): this thread's chunks of tile kt+1 from register
+  // stage e ^ 1 into LDS stage e ^ 1, and the next loads
+  auto stage = [&](int kt, auto E) {
+    constexpr int e = decltype(E)::value;
+    __bf16* nxt = smem + (e ^ 1) * STG;
+    if constexpr (V & 4) {
+      la.fetch(kb + (kt + 2) * BK, ke, ra[e]);
+      lb.fetch(kb + (kt + 2) * BK, ke, rb[e]);
+    }
+    if (kt + 1 < nk) {
+      la.commit3(nxt, PA, ra[e ^ 1]);
+      lb.commit3(nxt + 3 * PA, PB, rb[e ^ 1]);
+    }
+    if constexpr (!(V & 4)) {
+      la.fetch(kb + (kt + 3) * BK, ke, ra[e ^ 1]);
+      lb.fetch(kb + (kt + 3) * BK, ke, rb[e ^ 1]);
+    }
+  };
+  // Half 1 runs the same program one segment ahead: its commit segment of tile kt+1 lies between its MFMA
+  // segments of tiles kt and kt+1, against half 0's MFMA segment of tile kt+1.  (One MFMA site per tile
+  // parity: with both roles under a branch in every segment the accumulators went through 400+ spills.)
+  // The barriers of the two halves pair up in execution order, 2 nk on either path: half 1 has one more
+  // before the loop and one fewer at its last tile.
+  if (half1) {
+    stage(0, std::integral_constant<int, 0>{});
+    __syncthreads();
+  }
+  auto step = [&](int kt, auto E) {
+    constexpr int e = decltype(E)::value;
+    mma(smem + e * STG);
+    __syncthreads();
+    if (!half1) stage(kt, E);
+    else if (kt + 1 < nk) stage(kt + 1, std::integral_constant<int, e ^ 1>{});
+    if (!half1 || kt + 1 < nk) __syncthreads();
   };
   for (int kt = 0; kt < nk; kt += 2) {
     step(kt, std::integral_constant<int, 0>{});
@@ -831,6 +1046,21 @@ gemm_kernel_s6l(typename LA::Params pa, typename LB::Params pb, EP ep, int K, in
         const int j = j0 + wj * WTJ + b * 32 + r32;
         ep(i, j, acc[a][b][4 * g], acc[a][b][4 * g + 1], acc[a][b][4 * g + 2], acc[a][b][4 * g + 3]);
       }
+}
+
+// gemm_kernel_s6p with launch_gemm's K slicing
+template <class C, class LA, class LB, int V = 5, class EP>
+inline hipError_t launch_gemm_s6p(const typename LA::Params& pa, const typename LB::Params& pb, const EP& ep,
+                                  int Mi, int Nj, int K, int nsplit, hipStream_t st) {
+  if (Mi <= 0 || Nj <= 0 || K <= 0) return hipSuccess;
+  if (nsplit < 1) nsplit = 1;
+  int kchunk = (K + nsplit - 1) / nsplit;
+  kchunk = (kchunk + C::BK - 1) / C::BK * C::BK;
+  nsplit = (K + kchunk - 1) / kchunk;
+  dim3 grid((Nj + C::BJ - 1) / C::BJ, (Mi + C::BI - 1) / C::BI, nsplit);
+  hipLaunchKernelGGL((gemm_kernel_s6p<C, LA, LB, EP, V>), grid, dim3(C::NT), 0, st, pa, pb, ep, K, kchunk,
+                     tile_map(grid));
+  return hipGetLastError();
 }
 
 // Host-side launcher.  Mi/Nj are the D extents, K the reduction length,

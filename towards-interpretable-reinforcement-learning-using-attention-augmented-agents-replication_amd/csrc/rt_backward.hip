@@ -259,6 +259,35 @@ int lstm_wgrad(const T* dz, const T* xh, int rows, int h, int w, float* gW, hipS
     // C2 655 us at 18-way against 679 at 36 and 845 at 27, profiles/r05/ab/wgrad_s6l/)
     const int per_cu = split6l_of<CW>::value ? device_cus() : 512;
     const int ns = std::max(1, std::min(ab_int("AAA_WGRAD_SPLIT", std::max(1, per_cu / tiles)), rows / CW::BK));
+    // The production split-at-commit tile (8 waves, two register stages), AAA_WGRAD_S6_PAIRED:
+    // 1 (default) = the K loop in whole pairs of tiles and each commit issued among the MFMAs (gemm.h
+    // GemmCfgS6LK: the same sums per workgroup), 0 = the loop of gemm_kernel_s6l as it was; ablation
+    // builds: 2 = the two-segment paired kernel (gemm_kernel_s6p), 3 = the K loop in pairs alone.
+    // C2, two boxes: 603 / 621 (0), 587 / 605 (3), 573 / 588 (1), 643 / 666 (2) us, profiles/r07/ab/wgrad_pp/
+    if constexpr (s6p_of<CW>::value) {
+      int sched = env_int("AAA_WGRAD_S6_PAIRED", 1);
+#ifndef AAA_ABLATION
+      if (sched > 1) sched = 1;
+#endif
+      auto run = [&](auto cfg, const char* what, auto paired) -> int {
+        using CK = decltype(cfg);
+        TimerScope tim(AAA_TIMER_CORE_WGRAD, s, 2.0 * 512 * 1728 * rows,
+                       strf("register-staged %dx%d BK%d (fp32 as bf16x6 split products), %s, %d-way split-K atomics "
+                            "[kernel: %s+LdIm2colTB]", CW::BI, CW::BJ, CW::BK, what, ns,
+                            decltype(paired)::value ? "gemm_kernel_s6p" : "gemm_kernel_s6l+GemmCfgS6LK"));
+        if constexpr (decltype(paired)::value) HIPCHK((launch_gemm_s6p<CK, LA, LB>(pa, pb, ep, 512, 1728, rows, ns, s)));
+        else HIPCHK((launch_gemm<CK, LA, LB>(pa, pb, ep, 512, 1728, rows, ns, s)));
+        return AAA_OK;
+      };
+      if (sched == 1)
+        return run(GemmCfgS6LK<CW::BI, CW::BJ, CW::BK, CW::WI, CW::WJ, 2, 1>{},
+                   "K loop in pairs, commits among the MFMAs", std::false_type{});
+#ifdef AAA_ABLATION
+      if (sched == 2) return run(CW{}, "paired MFMA / commit segments", std::true_type{});
+      if (sched == 3)
+        return run(GemmCfgS6LK<CW::BI, CW::BJ, CW::BK, CW::WI, CW::WJ, 2, 0>{}, "K loop in pairs", std::false_type{});
+#endif
+    }
     TimerScope tim(AAA_TIMER_CORE_WGRAD, s, 2.0 * 512 * 1728 * rows,
                    strf("register-staged %dx%d BK%d%s, %d-way split-K atomics [kernel: gemm_kernel+%d, %d, %d, +LdIm2colTB]",
                         CW::BI, CW::BJ, CW::BK, split6_of<CW>::value ? " (fp32 as bf16x6 split products)" : "", ns,
