@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define AAA_ABI_VERSION 10
+#define AAA_ABI_VERSION 11
 
 enum aaa_status {
   AAA_OK = 0,
@@ -245,10 +245,26 @@ int aaa_pair_flag_at(float* dst, int* base, hipStream_t stream);
  *   AAA_WS_QUERY_HIDDEN1  (T*B, 72 nq) fp32: relu(query.model.2(.)), the
  *                         stateful core's query MLP (attention.py:184-198);
  *                         AAA_FLAG_STATEFUL_CORE only.
- * Frame f = t*B + b.  AAA_E_ARG for an unknown region or one the cfg does not
- * compute.  A test reads these masks to run the oracle's backward through the
- * same ReLU on/off pattern (tests/helpers.py hip_relu_masks). */
-enum aaa_ws_region { AAA_WS_ANSWER_HIDDEN = 0, AAA_WS_QUERY_HIDDEN0 = 1, AAA_WS_QUERY_HIDDEN1 = 2 };
+ * Frame f = t*B + b.  A test reads these masks to run the oracle's backward
+ * through the same ReLU on/off pattern (tests/helpers.py hip_relu_masks).
+ * ABI 11, fp32 configs only (bf16 and channel-quad-major geometries: AAA_E_ARG,
+ * as aaa_core_export): the operands and cotangents of the fp32 ConvLSTM GEMMs,
+ * read-only, M = B*h*w pixel rows per step, pixel-major, channel fastest:
+ *   AAA_WS_CORE_XH        (T+1, M, 192) fp32: slot t = [x_t | h_{t-1}], the
+ *                         recurrence's and the weight gradient's operand
+ *                         (slot T holds h_{T-1} only);
+ *   AAA_WS_CORE_DO        (T, M, 128) fp32: the readout's cotangent of h_t,
+ *                         valid after AAA_BWD_HEAD;
+ *   AAA_WS_CORE_DX        (T, M, 64) fp32: the cotangent of conv2's output
+ *                         x_t, valid after AAA_BWD_CORE.
+ * With aaa_core_export's gates / c_t / h_t these are everything a checker
+ * needs to evaluate the recurrence and its BPTT in fp64 on the kernels' own
+ * inputs (tests/f32_split_ref.py, tests/test_gpu_f32_split.py).
+ * AAA_E_ARG for an unknown region or one the cfg does not compute. */
+enum aaa_ws_region {
+  AAA_WS_ANSWER_HIDDEN = 0, AAA_WS_QUERY_HIDDEN0 = 1, AAA_WS_QUERY_HIDDEN1 = 2,
+  AAA_WS_CORE_XH = 3, AAA_WS_CORE_DO = 4, AAA_WS_CORE_DX = 5
+};
 int aaa_workspace_region(const aaa_cfg* cfg, int region, size_t* offset, size_t* bytes);
 
 /* ---- optional kernel timing (benchmarks) ----

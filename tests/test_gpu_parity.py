@@ -587,19 +587,31 @@ def test_c5_full_size_bf16_vs_emulated_oracle(cuda):
     kink_report(ref[4], rg, "C5 /255 frames")
 
 
-def test_f32_split6_accuracy(cuda, monkeypatch):
+@pytest.mark.parametrize("T,B,frames", [(20, 8, None), (3, 2, "8")])
+def test_f32_split6_accuracy(cuda, monkeypatch, T, B, frames):
     """The fp32 path's ConvLSTM weight gradient and batched dx on the bf16 MFMA
     with three-way split operands (gemm.h SPLIT6, AAA_F32_SPLIT6=1) are as
     accurate as on the fp32 MFMA: against the exact (fp64) evaluation of the
     reference op sequence, every gradient's error stays within 2x (+1e-7) of
-    the fp32-MFMA run's, and both within the 1e-4 criterion."""
-    T, B = 20, 8
+    the fp32-MFMA run's, and both within the 1e-4 criterion.  (20, 8) runs the
+    default dispatch, which at B = 8 is the per-step launches; (3, 2) forces
+    the frame-group forward and BPTT + dx (AAA_F32_FRAMES=8), so the claim
+    covers the kernels the headline config runs (kernel by kernel against
+    fp64 on their own inputs: test_gpu_f32_split.py)."""
     torch.set_num_threads(16)
+    if frames is not None:
+        monkeypatch.setenv("AAA_F32_FRAMES", frames)
     ref = _oracle(T, B, dtype=torch.float64)
     errs = {}
     for mode in ("0", "1"):
         monkeypatch.setenv("AAA_F32_SPLIT6", mode)
-        out = _run_unroll(_agent(cuda), T, B, cuda)
+        N.timing_enable(True)
+        try:
+            out = _run_unroll(_agent(cuda), T, B, cuda)
+            var = N.timing_stats(N.TIMER_FWD_STEP)["variant"]
+        finally:
+            N.timing_enable(False)
+        assert ("8 WG per frame" in var) == (frames == "8"), var
         _compare(out, ref, RTOL, f"split6={mode}: ")
         errs[mode] = {n: rel_err(out[3][n].numpy().astype(np.float64), ref[3][n].numpy())
                       for n in ref[3] if float(ref[3][n].norm()) > 0}

@@ -33,7 +33,39 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_abi_version():
-    assert N.load().aaa_abi_version() == N.ABI_VERSION == 10
+    assert N.load().aaa_abi_version() == N.ABI_VERSION == 11
+
+
+def test_core_checker_regions():
+    """ABI 11: the fp32 recurrence's operand slots, the readout's cotangent of
+    h_t and the cotangent of conv2's output as workspace regions -- their sizes,
+    that they lie inside the workspace without overlapping, and AAA_E_ARG for a
+    bf16 config (as aaa_core_export refuses what it cannot give as fp32 rows)."""
+    lib = N.load()
+    src = open(HEADER).read()
+    enum = dict((k, int(v)) for k, v in re.findall(r"AAA_WS_([A-Z0-9_]+)\s*=\s*(\d+)", src))
+    assert enum == {"ANSWER_HIDDEN": 0, "QUERY_HIDDEN0": 1, "QUERY_HIDDEN1": 2, "CORE_XH": 3, "CORE_DO": 4, "CORE_DX": 5}
+    for name, val in enum.items():
+        assert getattr(N, "WS_" + name) == val, name
+    T, B, P = 20, 32, 121
+    cfg = N.Cfg(B, T, 84, 84, 4, 18, N.F32, 0)
+    ws = lib.aaa_workspace_bytes(ctypes.byref(cfg))
+    spans = []
+    for region, nbytes in ((N.WS_CORE_XH, (T + 1) * B * P * 192 * 4), (N.WS_CORE_DO, T * B * P * 128 * 4),
+                           (N.WS_CORE_DX, T * B * P * 64 * 4)):
+        off, nb = ctypes.c_size_t(), ctypes.c_size_t()
+        assert lib.aaa_workspace_region(ctypes.byref(cfg), region, ctypes.byref(off), ctypes.byref(nb)) == 0
+        assert nb.value == nbytes and off.value % 16 == 0 and off.value + nb.value <= ws
+        spans.append((off.value, off.value + nb.value))
+    spans.sort()
+    assert all(a[1] <= b[0] for a, b in zip(spans, spans[1:])), spans
+    off, nb = ctypes.c_size_t(), ctypes.c_size_t()
+    bf = N.Cfg(B, T, 84, 84, 4, 18, N.BF16, 0)
+    for region in (N.WS_CORE_XH, N.WS_CORE_DO, N.WS_CORE_DX):
+        assert lib.aaa_workspace_region(ctypes.byref(bf), region, ctypes.byref(off), ctypes.byref(nb)) == -1
+        assert b"region" in lib.aaa_last_error()
+    assert lib.aaa_workspace_region(ctypes.byref(bf), N.WS_ANSWER_HIDDEN, ctypes.byref(off), ctypes.byref(nb)) == 0
+    assert lib.aaa_workspace_region(ctypes.byref(cfg), 6, ctypes.byref(off), ctypes.byref(nb)) == -1
 
 
 @pytest.mark.parametrize("H,W,hw", [(84, 84, (11, 11)), (168, 168, (21, 21)), (210, 160, (27, 20))])

@@ -107,8 +107,13 @@ static int cell_bwd_impl(const CellLayout& C, const char* pk, const float* dh1, 
     EpiConvLstmBwd<T, GT> ep{dx ? dx : (float*)(ws + C.dX), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                              dh0, 0, M, 0, nullptr};
     const ConvGeo g = ConvGeo{512, 512, 0, C.h, C.w, C.h, C.w, 3, 1, 1, 1}.prep();
-    HIPCHK((step_gemm<CfgFor<T>, false>((const T*)(pk + C.k_WdTl), 4608, 192, (const T*)dZ, g, M,
-                                         (uint32_t)((size_t)M * 512 * C.esz), ep, 192, 4608, st)));
+    // fp32: the 4-way in-WG split-K tile (the learner's AAA_BPTT_TILE 2).  One wave's K = 4608 chain of fp32
+    // MFMA accumulations put dx / dh0 at 1.2e-6 of fp64 -- half of what a split-product kernel that lost a lo
+    // part would show, past the e2 / 2 gate of tests/test_gpu_f32_split.py; four chains of 1152 are at
+    // sqrt(1/4) of that (DESIGN.md "fp32 split products: accuracy")
+    using CD = std::conditional_t<std::is_same<T, float>::value, CFK4, CfgFor<T>>;
+    HIPCHK((step_gemm<CD, false>((const T*)(pk + C.k_WdTl), 4608, 192, (const T*)dZ, g, M,
+                                  (uint32_t)((size_t)M * 512 * C.esz), ep, 192, 4608, st)));
     return AAA_OK;
   };
   int rc = gates_f16(C.dt, M) ? run(_Float16{}) : run(float{});

@@ -136,6 +136,18 @@ int aaa_workspace_region(const aaa_cfg* cfg, int region, size_t* offset, size_t*
     case AAA_WS_QUERY_HIDDEN1:
       if (!L.sc) break;
       *offset = L.q2s; *bytes = F * (size_t)L.qd * 4; return AAA_OK;
+    // the fp32 recurrence's operands and cotangents (row-major fp32 only: a checker's fp64 reference of the
+    // ConvLSTM GEMMs reads the kernels' own inputs here)
+    case AAA_WS_CORE_XH:
+    case AAA_WS_CORE_DO:
+    case AAA_WS_CORE_DX: {
+      if (L.dt != AAA_F32 || cqm_layout(L)) break;
+      const size_t M = (size_t)L.B * L.P;
+      if (region == AAA_WS_CORE_XH) { *offset = L.XH; *bytes = (size_t)(L.T + 1) * M * 192 * 4; }
+      else if (region == AAA_WS_CORE_DO) { *offset = L.dO; *bytes = F * L.P * 128 * 4; }
+      else { *offset = L.dY2; *bytes = F * L.P * 64 * 4; }
+      return AAA_OK;
+    }
     default: break;
   }
   return fail(AAA_E_ARG, "workspace_region: region %d not computed by this cfg", region);

@@ -47,14 +47,16 @@ class UnrollRunner:
     def state_shape(self):
         return (self.B, self.h, self.w, 128)
 
-    def workspace_region(self, workspace, region: int):
-        """A forward product inside ``workspace`` (aaa_workspace_region): an
-        (T*B, n) fp32 view, e.g. N.WS_ANSWER_HIDDEN = relu(answer_processor.0)."""
+    def workspace_region(self, workspace, region: int, shape=None):
+        """A product inside ``workspace`` (aaa_workspace_region): an fp32 view,
+        (T*B, n) by default, e.g. N.WS_ANSWER_HIDDEN = relu(answer_processor.0),
+        or of ``shape`` (one -1 allowed), e.g. N.WS_CORE_XH as (T+1, B*h*w, 192)."""
         off, nb = ctypes.c_size_t(), ctypes.c_size_t()
         N.check(self.lib.aaa_workspace_region(ctypes.byref(self.cfg), int(region), ctypes.byref(off),
                                               ctypes.byref(nb)), "workspace_region")
         F = self.T * self.B
-        return workspace[off.value:off.value + nb.value].view(torch.float32).view(F, nb.value // (4 * F))
+        flat = workspace[off.value:off.value + nb.value].view(torch.float32)
+        return flat.view(F, nb.value // (4 * F)) if shape is None else flat.view(*shape)
 
     def relu_masks(self, workspace):
         """The on/off pattern of every ReLU the hand-written backward masks with,
