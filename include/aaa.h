@@ -375,8 +375,8 @@ int aaa_sample_actions(int B, int A, const float* logits, unsigned long long see
  * LSTMCell, heads + draw) instead of aaa_forward's whole-batch kernels.
  * Results equal aaa_forward with T = 1, h0 = *h, c0 = *c up to fp32
  * summation order; the draw is bit-identical to aaa_sample_actions on those
- * logits.  cfg: T = 1, dtype AAA_F32, no AAA_FLAG_STATEFUL_CORE (those use
- * aaa_forward); ``packed`` from aaa_pack_weights with the same cfg.  h, c
+ * logits.  cfg: T = 1, dtype AAA_F32, no AAA_FLAG_STATEFUL_CORE (bf16 and
+ * T > 1 use aaa_forward, the stateful core aaa_actor_step_core); ``packed`` from aaa_pack_weights with the same cfg.  h, c
  * (B, h, w, 128) are read and overwritten with the step's state (zero them for
  * reset()).  actions == NULL skips the draw (seed/counter/logp/dlogp ignored). */
 typedef struct aaa_actor_io {
@@ -407,6 +407,38 @@ typedef struct aaa_actor_io {
 } aaa_actor_io;
 size_t aaa_actor_workspace_bytes(const aaa_cfg* cfg);
 int aaa_actor_step(const aaa_cfg* cfg, const aaa_actor_io* io, hipStream_t stream);
+
+/* ---- actor: one environment step, stateful policy core ----
+ * aaa_actor_step for the agent of AAA_FLAG_STATEFUL_CORE (the reference's
+ * `else` branch, attention.py:324-331, 356-358): this step's queries are
+ * Q_t = QueryNetwork(core_h) (attention.py:184-198), one set per row, and the
+ * LSTMCell runs from (core_h, core_c).  Seven launches: the first layer of the
+ * query MLP, then the chain of aaa_actor_step with the MLP's other two layers
+ * riding as extra workgroups of its vision and ConvLSTM launches, the readout
+ * on per-row queries and the LSTMCell reading [answer | core_h] against
+ * [W_ih | W_hh].
+ * Results equal aaa_forward with the flag, T = 1, h0 = *h, c0 = *c,
+ * core_h0 = *core_h, core_c0 = *core_c up to fp32 summation order; zeroing
+ * all four states is reset().  The draw, gates, h_out / c_out, attn and the
+ * uint8 / fp32 frames are as in aaa_actor_step.  cfg: T = 1, dtype AAA_F32,
+ * B <= 16, AAA_FLAG_STATEFUL_CORE set; ``packed`` from aaa_pack_weights with
+ * the same cfg; io->workspace of aaa_actor_core_workspace_bytes().  Anything
+ * else is AAA_E_ARG (the workspace query returns 0), checked before the device
+ * is touched.  params, packed, basis, h, c, workspace, core_h, core_c and a
+ * non-NULL core_h_out must be 16-byte aligned (AAA_E_ALIGN).
+ * These two symbols were added after ABI version 11 without a bump (the
+ * change is purely additive): probe for them by name, not by version. */
+typedef struct aaa_actor_core_io {
+  float* core_h;             /* (B, 256) prev_output: read, and overwritten with
+                                h_t unless core_h_out                          */
+  float* core_c;             /* (B, 256) prev_hidden: likewise                 */
+  float* core_h_out;         /* (B, 256) or NULL                               */
+  float* core_c_out;         /* (B, 256) or NULL                               */
+  float* query;              /* (B, nq, 72) or NULL: this step's Q_t (checkers) */
+} aaa_actor_core_io;
+size_t aaa_actor_core_workspace_bytes(const aaa_cfg* cfg);
+int aaa_actor_step_core(const aaa_cfg* cfg, const aaa_actor_io* io, const aaa_actor_core_io* core,
+                        hipStream_t stream);
 
 /* ---- single-kernel entry points (unit tests against PyTorch fp32) ---- */
 

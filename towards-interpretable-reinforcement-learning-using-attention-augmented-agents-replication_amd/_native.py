@@ -32,6 +32,8 @@ EXPORTS = (
     "aaa_actor_workspace_bytes", "aaa_actor_step", "aaa_pair_status", "aaa_pair_flag", "aaa_pair_flag_at",
     "aaa_adam_step_guarded", "aaa_adam_step_counted", "aaa_workspace_region",
     "aaa_core_elem_bytes", "aaa_forward_phases", "aaa_core_export", "aaa_core_import",
+    # added after ABI 11 without a bump (purely additive; include/aaa.h): probed by name
+    "aaa_actor_core_workspace_bytes", "aaa_actor_step_core",
 )
 # include/aaa.h enum aaa_timer
 TIMER_FWD_STEP, TIMER_BPTT_STEP, TIMER_CORE_WGRAD, TIMER_ATTN_FWD, TIMER_ATTN_BWD = 0, 1, 2, 3, 4
@@ -74,6 +76,11 @@ class ActorIO(ctypes.Structure):
         ("seed", ctypes.c_ulonglong), ("counter", ctypes.c_void_p), ("actions", ctypes.c_void_p),
         ("logp", ctypes.c_void_p), ("dlogp_dlogits", ctypes.c_void_p), ("gates", ctypes.c_void_p),
         ("h_out", ctypes.c_void_p), ("c_out", ctypes.c_void_p)]
+
+
+class ActorCoreIO(ctypes.Structure):
+    """include/aaa.h aaa_actor_core_io (aaa_actor_step_core)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("core_h", "core_c", "core_h_out", "core_c_out", "query")]
 
 
 class AdamHP(ctypes.Structure):
@@ -165,6 +172,8 @@ def load(path: str = LIB_PATH):
             "aaa_divisor_log": (I, [I, ctypes.POINTER(ctypes.c_uint), I]),
             "aaa_actor_workspace_bytes": (S, [CP]),
             "aaa_actor_step": (I, [CP, ctypes.POINTER(ActorIO), P]),
+            "aaa_actor_core_workspace_bytes": (S, [CP]),
+            "aaa_actor_step_core": (I, [CP, ctypes.POINTER(ActorIO), ctypes.POINTER(ActorCoreIO), P]),
             "aaa_pair_status": (I, [P, I]),
         }
         ab_override = "AAA_LIB" in os.environ

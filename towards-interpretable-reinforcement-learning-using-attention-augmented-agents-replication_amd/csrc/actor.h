@@ -2,6 +2,10 @@
 // few rows (the acting half of main_mp.py:49-59 / test_model.py:42-73), fp32,
 // as six launches sized for B <= 16 instead of the learner's whole-batch
 // kernels.  Pointers are resolved by the runtime from the aaa_cfg layout.
+// aaa_actor_step_core is the same chain for the stateful policy core
+// (attention.py:324-331, 356-358): seven launches -- the query MLP's first
+// layer in front, its other two riding on the vision and ConvLSTM launches,
+// the readout on per-row queries, and the LSTMCell from the carried (h, c).
 #pragma once
 #include "common.h"
 
@@ -19,7 +23,8 @@ struct ActorParams {
   const float *Wp1, *b1;     // conv1 [32][256] RGBx, bias (32)
   const float *Wp2, *b2;     // conv2 [64][512], bias (64)
   const float *WpXH, *bl;    // ConvLSTM [512][1728] rows 4ch+g, bias [512]
-  const float* Q;            // constant query (nq*72)
+  const float* Q;            // constant query (nq*72); stateful core: this step's Q_t (B, nq*72)
+  int q_stride;              // floats between the rows' queries: 0 = the constant query
   const float *W1p, *a0b;    // answer_processor.0 [512][ans_ld], bias
   const float *A2W, *a2b;    // answer_processor.2 [256][512], bias
   const float *Wihp, *blc;   // LSTMCell [1024][256] rows 4u+g, b_ih + b_hh
@@ -44,6 +49,13 @@ struct ActorParams {
   int* actions;
   float* logp;
   float* jac;
+  // stateful policy core (core_h != NULL; aaa_actor_step_core)
+  float *core_h, *core_c;          // (B, 256) prev_output / prev_hidden, in (and out unless *_out)
+  float *core_h_out, *core_c_out;  // (B, 256) or NULL
+  float* query_out;                // (B, nq*72) or NULL: a copy of Q_t
+  const float *Q0W, *Q0B, *Q2W, *Q2B, *Q4W, *Q4B;   // QueryNetwork, torch [out][in]
+  const float* Wihhp;              // LSTMCell [1024][512] = [W_ih | W_hh], rows 4u+g
+  float *Qt, *q1, *q2;             // workspace: Q_t (B, nq*72) and the MLP's hidden rows (B,128), (B, nq*72)
 };
 
 hipError_t actor_launch(const ActorParams& p, hipStream_t st);

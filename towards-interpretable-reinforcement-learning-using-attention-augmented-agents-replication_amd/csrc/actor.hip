@@ -15,6 +15,13 @@
 // (the ConvLSTM's K slices, the readout's position chunks) finish inside
 // their launch: the last workgroup to arrive at a counter merges the partials.
 //
+// The stateful policy core (aaa_actor_step_core; attention.py:324-331,
+// 356-358) is the same chain with the query MLP (Q_t = QueryNetwork(core_h),
+// one query set per row, read by the readout through q_stride) -- its first
+// layer one launch in front, the other two riding as extra workgroups of the
+// vision and ConvLSTM launches -- and k_act_lstmcell_core in place of the
+// zero-state LSTMCell: seven launches, one stream, the same hand-offs.
+//
 // Numerics: fp32 throughout (the ConvLSTM and conv1 on exact-fp32
 // v_mfma_f32_16x16x4_f32, the rest fp32 FMA); only the summation order
 // differs from the learner path (tests/test_gpu_actor.py compares both at
@@ -47,6 +54,58 @@ __device__ __forceinline__ f32x4 mfma4(float a, float b, const f32x4& c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
+// ------------------------------------------- query MLP (stateful core) -----
+// One layer of QueryNetwork (attention.py:184-198) on the B rows: y = W x + b
+// (ReLU on the first two), W in torch's [N][K] layout from the flat params.
+// One wave per output row: its K <= 256 * NIT weights in registers (float4
+// slices at clamped offsets, as k_act_ans0), then the loop over the rows.
+// 256 -> 128 -> 72 nq -> 72 nq.  Q_t depends only on the previous step's
+// core_h, so only the first layer is a launch of its own (k_act_qlin, in
+// front of the vision launch); the second rides as extra workgroups of the
+// vision launch and the third of the ConvLSTM launch (their RIDE variants:
+// blockIdx.x past the launch's own grid), instead of two more serial kernels
+// (three launches in front measured 57.4 / 77.3 us per B = 1 step at 84x84 /
+// 210x160, the riders 53.5 / 73.4; profiles/r08/actor_core).
+struct QLayer {
+  const float *W, *bias, *x;
+  float *y, *y2;   // y2: a second copy of the output, or NULL
+  int K, N;
+};
+
+template <int NIT, bool RELU>
+__device__ __forceinline__ void qlin_row(const QLayer& q, int row, int lane, int B) {
+  if (row >= q.N) return;
+  const float* wr = q.W + (size_t)row * q.K;
+  f32x4 wv[NIT];
+  int k[NIT];
+#pragma unroll
+  for (int i = 0; i < NIT; ++i) {
+    k[i] = min(4 * lane + 256 * i, q.K - 4);
+    wv[i] = ld4(wr + k[i]);
+  }
+  const float b = q.bias[row];
+  for (int f = 0; f < B; ++f) {
+    f32x4 xv[NIT];
+#pragma unroll
+    for (int i = 0; i < NIT; ++i) xv[i] = ld4(q.x + (size_t)f * q.K + k[i]);
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < NIT; ++i)
+      if (4 * lane + 256 * i < q.K) s += dot4(wv[i], xv[i]);
+    s = wsum(s) + b;
+    if (RELU) s = fmaxf(s, 0.f);
+    if (lane == 0) {
+      q.y[(size_t)f * q.N + row] = s;
+      if (q.y2) q.y2[(size_t)f * q.N + row] = s;
+    }
+  }
+}
+
+template <int NIT, bool RELU>
+__global__ void __launch_bounds__(256) k_act_qlin(QLayer q, int B) {
+  qlin_row<NIT, RELU>(q, blockIdx.x * 4 + (threadIdx.x >> 6), threadIdx.x & 63, B);
+}
+
 // ------------------------------------------------------------ vision ------
 // One workgroup per (conv2 output pixel, frame): VisionNetwork.vision_cnn
 // (attention.py:155-170 on X.transpose(1,3), Q3: the packed weights carry
@@ -60,8 +119,15 @@ __device__ __forceinline__ f32x4 mfma4(float a, float b, const f32x4& c) {
 // channels, lanes along K).
 constexpr int kPatchLd = 81;   // floats per patch row: 4*81 = 4 (mod 64) spreads the 4 window rows over banks
 
-template <typename TI>
-__global__ void __launch_bounds__(256) k_act_vision(ActorParams p) {
+template <typename TI, bool RIDE = false>
+__global__ void __launch_bounds__(256) k_act_vision(ActorParams p, QLayer ql = QLayer{}) {
+  if constexpr (RIDE) {   // the query MLP's second layer: workgroups past the P pixels (of frame 0's row of the grid)
+    if ((int)blockIdx.x >= p.P) {
+      if (blockIdx.y == 0)
+        qlin_row<1, true>(ql, ((int)blockIdx.x - p.P) * 4 + (threadIdx.x >> 6), threadIdx.x & 63, p.B);
+      return;
+    }
+  }
   __shared__ float patch[20 * kPatchLd];
   __shared__ __attribute__((aligned(16))) float red[4][2][64][4];
   __shared__ __attribute__((aligned(16))) float y1w[16 * 32];
@@ -172,7 +238,16 @@ constexpr int kSC1 = 16;                      // buffer cache policy: sc1 (cross
 constexpr int kLsPitch = 20;                  // floats per LDS row: 80 B puts 16 rows on disjoint banks
 constexpr int kLsSteps = 108 / kActLstmKS;    // K blocks of 16 per slice
 
-__global__ void __launch_bounds__(512) k_act_convlstm(ActorParams p, int npt) {
+template <int RIDE = 0>   // RIDE = NIT of the query MLP's third layer riding on this launch (0: none)
+__global__ void __launch_bounds__(512) k_act_convlstm(ActorParams p, int npt, QLayer ql = QLayer{}) {
+  if constexpr (RIDE > 0) {   // workgroups past the launch's own 8 * kActLstmKS * npt tiles
+    const int base = 8 * kActLstmKS * npt;
+    if ((int)blockIdx.x >= base) {
+      if (blockIdx.y == 0)
+        qlin_row<RIDE, false>(ql, ((int)blockIdx.x - base) * 8 + (threadIdx.x >> 6), threadIdx.x & 63, p.B);
+      return;
+    }
+  }
   __shared__ __attribute__((aligned(16))) float Wt[2][64 * kLsPitch];
   __shared__ __attribute__((aligned(16))) float Bt[2][64 * kLsPitch];
   __shared__ int is_last;
@@ -287,7 +362,7 @@ __global__ void __launch_bounds__(256) k_act_attn(ActorParams p, int nch) {
   const float* O = p.Hs + (size_t)f * P * 128;
   const float* S = p.basis;
   const int p0 = c * kAttnChunk, np = min(kAttnChunk, P - p0);
-  for (int i = tid; i < NQ * 72; i += 256) Qs[i] = p.Q[i];
+  for (int i = tid; i < NQ * 72; i += 256) Qs[i] = p.Q[(size_t)f * p.q_stride + i];   // q_stride 0: the constant query
   {   // this chunk's share of h_t -> the carried state
     const int n4 = P * 32, per = (n4 + nch - 1) / nch;
     const f32x4* src = reinterpret_cast<const f32x4*>(O);
@@ -557,18 +632,97 @@ __global__ void __launch_bounds__(256) k_act_lstmcell(ActorParams p) {
   if (is_last) heads_draw(p, lg);
 }
 
+// --------------------------------------- LSTMCell (carried state) + heads --
+// policy_core from (core_h, core_c) = (prev_output, prev_hidden)
+// (attention.py:356-358): one wave per unit u, its four gate rows 4u..4u+3 of
+// [W_ih | W_hh] ([1024][512]) against [AO_f | core_h_f]; c_t = f c_{t-1} +
+// i g~, h_t = o tanh(c_t) -- the learner's EpiLstmCellFwdS.  c is per unit
+// and updated in place.  Every workgroup reads all of core_h, so h_t is
+// staged in LH (sc1 hand-off, as k_act_lstmcell) and the last workgroup to
+// arrive -- every other one has finished its reads by then -- commits it to
+// core_h (or core_h_out) after the heads and the draw.
+__global__ void __launch_bounds__(256) k_act_lstmcell_core(ActorParams p) {
+  __shared__ float lg[16 * 256];
+  __shared__ int is_last;
+  const int tid = threadIdx.x, lane = tid & 63, u = blockIdx.x * 4 + (tid >> 6);
+  f32x4 wx[4], wh[4];
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    const float* wr = p.Wihhp + (size_t)(4 * u + g) * 512 + 4 * lane;
+    wx[g] = ld4(wr);
+    wh[g] = ld4(wr + 256);
+  }
+  const f32x4 b = ld4(p.blc + 4 * u);
+  const __amdgpu_buffer_rsrc_t rh = make_rsrc(p.LH, (uint32_t)(p.B * 256 * 4));
+  float* cdst = p.core_c_out ? p.core_c_out : p.core_c;
+  for (int f = 0; f < p.B; ++f) {
+    const f32x4 x = ld4(p.AO + (size_t)f * 256 + 4 * lane);
+    const f32x4 hp = ld4(p.core_h + (size_t)f * 256 + 4 * lane);
+    const float cp = p.core_c[(size_t)f * 256 + u];
+    float z[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) z[g] = wsum(dot4(wx[g], x) + dot4(wh[g], hp));
+    if (lane == 0) {
+      const float gi = sigm_acc(z[0] + b[0]), gf = sigm_acc(z[1] + b[1]);
+      const float gc = tanhf(z[2] + b[2]), go = sigm_acc(z[3] + b[3]);
+      const float c = gf * cp + gi * gc;
+      cdst[(size_t)f * 256 + u] = c;
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, go * tanhf(c)), rh,
+                                            (uint32_t)((f * 256 + u) * 4), 0, kSC1);
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (tid == 0) {
+    const int old = __hip_atomic_fetch_add(p.zcnt + p.B * 8 * actor_pix_tiles(p.P) + p.B, 1, __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_AGENT);
+    if (old == (int)gridDim.x - 1) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    is_last = old == (int)gridDim.x - 1;
+  }
+  __syncthreads();
+  if (!is_last) return;
+  heads_draw(p, lg);
+  f32x4* hd = reinterpret_cast<f32x4*>(p.core_h_out ? p.core_h_out : p.core_h);
+  for (int i = tid; i < p.B * 64; i += 256)
+    hd[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rh, (uint32_t)(i * 16), 0, kSC1));
+}
+
 }  // namespace
 
 hipError_t actor_launch(const ActorParams& p, hipStream_t st) {
   if (p.B < 1 || p.B > 16 || (p.nq != 4 && p.nq != 8) || p.A < 1 || p.A > 256 || p.ans_ld % 4 ||
       p.ans_ld > 2304 || actor_chunks(p.P) > kActMaxChunks)
     return hipErrorInvalidValue;
-  if (p.u8)
-    hipLaunchKernelGGL(k_act_vision<uint8_t>, dim3(p.P, p.B), dim3(256), 0, st, p);
-  else
-    hipLaunchKernelGGL(k_act_vision<float>, dim3(p.P, p.B), dim3(256), 0, st, p);
   const int npt = actor_pix_tiles(p.P);
-  hipLaunchKernelGGL(k_act_convlstm, dim3(8 * kActLstmKS * npt, p.B), dim3(512), 0, st, p, npt);
+  if (p.core_h) {   // stateful core: Q_t = QueryNetwork(core_h), read per row by the readout
+    const int qd = 72 * p.nq;
+    if (!p.core_c || !p.Qt || p.Q != p.Qt || p.q_stride != qd) return hipErrorInvalidValue;
+    const QLayer l0{p.Q0W, p.Q0B, p.core_h, p.q1, nullptr, 256, 128};
+    const QLayer l2{p.Q2W, p.Q2B, p.q1, p.q2, nullptr, 128, qd};
+    const QLayer l4{p.Q4W, p.Q4B, p.q2, p.Qt, p.query_out, qd, qd};
+    hipLaunchKernelGGL((k_act_qlin<1, true>), dim3(32), dim3(256), 0, st, l0, p.B);
+    // riders: qd / 4 workgroups of 4 waves on the vision launch, qd / 8 of 8 waves on the ConvLSTM launch
+    // (rounded up to a multiple of 8 so that frame f's tiles keep their blockIdx % 8 -> XCD mapping)
+    const int rv = qd / 4, rl = (qd / 8 + 7) / 8 * 8;
+    if (p.u8)
+      hipLaunchKernelGGL((k_act_vision<uint8_t, true>), dim3(p.P + rv, p.B), dim3(256), 0, st, p, l2);
+    else
+      hipLaunchKernelGGL((k_act_vision<float, true>), dim3(p.P + rv, p.B), dim3(256), 0, st, p, l2);
+    if (p.nq == 4)
+      hipLaunchKernelGGL(k_act_convlstm<2>, dim3(8 * kActLstmKS * npt + rl, p.B), dim3(512), 0, st, p, npt, l4);
+    else
+      hipLaunchKernelGGL(k_act_convlstm<3>, dim3(8 * kActLstmKS * npt + rl, p.B), dim3(512), 0, st, p, npt, l4);
+  } else {
+    if (p.q_stride) return hipErrorInvalidValue;
+    if (p.u8)
+      hipLaunchKernelGGL(k_act_vision<uint8_t>, dim3(p.P, p.B), dim3(256), 0, st, p, QLayer{});
+    else
+      hipLaunchKernelGGL(k_act_vision<float>, dim3(p.P, p.B), dim3(256), 0, st, p, QLayer{});
+    hipLaunchKernelGGL(k_act_convlstm<0>, dim3(8 * kActLstmKS * npt, p.B), dim3(512), 0, st, p, npt, QLayer{});
+  }
   const int nch = actor_chunks(p.P);
   if (p.nq == 4)
     hipLaunchKernelGGL(k_act_attn<4>, dim3(nch, p.B), dim3(256), 0, st, p, nch);
@@ -579,7 +733,10 @@ hipError_t actor_launch(const ActorParams& p, hipStream_t st) {
   else
     hipLaunchKernelGGL(k_act_ans0<8>, dim3(128, p.B), dim3(256), 0, st, p);
   hipLaunchKernelGGL(k_act_ans2, dim3(64), dim3(256), 0, st, p);
-  hipLaunchKernelGGL(k_act_lstmcell, dim3(64), dim3(256), 0, st, p);
+  if (p.core_h)
+    hipLaunchKernelGGL(k_act_lstmcell_core, dim3(64), dim3(256), 0, st, p);
+  else
+    hipLaunchKernelGGL(k_act_lstmcell, dim3(64), dim3(256), 0, st, p);
   return hipGetLastError();
 }
 

@@ -428,44 +428,62 @@ int aaa_sample_actions(int B, int A, const float* logits, unsigned long long see
 // Workspace: conv2 output X (B,P,64), h_t Hs (B,P,128), hid1 (B,512), AO (B,256), LH (B,256),
 // the ConvLSTM's split-K partial tiles, the tile and readout counters, the attention logits,
 // the readout's chunk partials and the answer row (actor.h).
-static int actor_layout(const aaa_cfg* cfg, Layout& L, size_t off[10], size_t* total) {
+// The stateful-core entry (core = true) adds Q_t (B, nq*72) and the query MLP's two hidden rows.
+constexpr int kActRegions = 13;
+static int actor_layout(const aaa_cfg* cfg, Layout& L, size_t off[kActRegions], size_t* total, bool core = false) {
   int r = build_layout(cfg, L);
   if (r) return r;
-  if (cfg->T != 1) return fail(AAA_E_ARG, "actor_step: T must be 1 (got %d)", cfg->T);
-  if (cfg->dtype != AAA_F32) return fail(AAA_E_ARG, "actor_step: fp32 weights only (bf16 agents use aaa_forward)");
-  if (L.sc) return fail(AAA_E_ARG, "actor_step: the stateful policy core uses aaa_forward");
-  if (cfg->B > 16) return fail(AAA_E_ARG, "actor_step: B <= 16 (got %d); larger batches use aaa_forward", cfg->B);
+  const char* who = core ? "actor_step_core" : "actor_step";
+  if (cfg->T != 1) return fail(AAA_E_ARG, "%s: T must be 1 (got %d)", who, cfg->T);
+  if (cfg->dtype != AAA_F32) return fail(AAA_E_ARG, "%s: fp32 weights only (bf16 agents use aaa_forward)", who);
+  if (L.sc && !core) return fail(AAA_E_ARG, "actor_step: the stateful policy core uses aaa_actor_step_core");
+  if (!L.sc && core) return fail(AAA_E_ARG, "actor_step_core: cfg lacks AAA_FLAG_STATEFUL_CORE (use aaa_actor_step)");
+  if (cfg->B > 16) return fail(AAA_E_ARG, "%s: B <= 16 (got %d); larger batches use aaa_forward", who, cfg->B);
   if (actor_chunks(L.P) > kActMaxChunks)
-    return fail(AAA_E_ARG, "actor_step: a %dx%d grid exceeds the readout's %d position chunks; use aaa_forward",
+    return fail(AAA_E_ARG, "%s: a %dx%d grid exceeds the readout's %d position chunks; use aaa_forward", who,
                 L.h, L.w, kActMaxChunks);
   const size_t B = cfg->B, P = L.P;
   const size_t nt = 8 * (size_t)actor_pix_tiles(L.P), nch = actor_chunks(L.P), nq = L.nq;
-  const size_t sz[10] = {B * P * 64 * 4, B * P * 128 * 4, B * 512 * 4, B * 256 * 4, B * 256 * 4,
-                         B * nt * kActLstmKS * 4096 * 4, (B * nt + B + 1) * 4, B * P * nq * 4,
-                         B * nch * nq * kAttnPart * 4, B * (size_t)L.ans_ld * 4};
+  const size_t qc = core ? 1 : 0;
+  const size_t sz[kActRegions] = {B * P * 64 * 4, B * P * 128 * 4, B * 512 * 4, B * 256 * 4, B * 256 * 4,
+                                  B * nt * kActLstmKS * 4096 * 4, (B * nt + B + 1) * 4, B * P * nq * 4,
+                                  B * nch * nq * kAttnPart * 4, B * (size_t)L.ans_ld * 4,
+                                  qc * B * L.qd * 4, qc * B * 128 * 4, qc * B * L.qd * 4};
   size_t o = 0;
-  for (int i = 0; i < 10; ++i) { off[i] = o; o = al256(o + sz[i]); }
+  for (int i = 0; i < kActRegions; ++i) { off[i] = o; o = al256(o + sz[i]); }
   *total = o;
   return AAA_OK;
 }
 
 size_t aaa_actor_workspace_bytes(const aaa_cfg* cfg) {
   Layout L;
-  size_t off[10], tot = 0;
+  size_t off[kActRegions], tot = 0;
   return actor_layout(cfg, L, off, &tot) ? 0 : tot;
 }
 
-int aaa_actor_step(const aaa_cfg* cfg, const aaa_actor_io* io, hipStream_t stream) {
+size_t aaa_actor_core_workspace_bytes(const aaa_cfg* cfg) {
   Layout L;
-  size_t off[10], tot = 0;
-  int r = actor_layout(cfg, L, off, &tot);
+  size_t off[kActRegions], tot = 0;
+  return actor_layout(cfg, L, off, &tot, true) ? 0 : tot;
+}
+
+static int actor_step_impl(const aaa_cfg* cfg, const aaa_actor_io* io, const aaa_actor_core_io* core, bool is_core,
+                           hipStream_t stream) {
+  Layout L;
+  size_t off[kActRegions], tot = 0;
+  int r = actor_layout(cfg, L, off, &tot, is_core);
   if (r) return r;
+  const char* who = is_core ? "actor_step_core" : "actor_step";
   if (!io || !io->params || !io->packed || !io->basis || !io->frames || !io->h || !io->c || !io->logits ||
       !io->values || !io->workspace)
-    return fail(AAA_E_ARG, "actor_step: NULL argument");
+    return fail(AAA_E_ARG, "%s: NULL argument", who);
+  if (is_core && (!core || !core->core_h || !core->core_c))
+    return fail(AAA_E_ARG, "actor_step_core: NULL core state (core, core_h and core_c are required)");
   if (!aligned16(io->packed) || !aligned16(io->basis) || !aligned16(io->h) || !aligned16(io->c) ||
       !aligned16(io->workspace) || !aligned16(io->params))
-    return fail(AAA_E_ALIGN, "actor_step: params, packed, basis, h, c and workspace must be 16-byte aligned");
+    return fail(AAA_E_ALIGN, "%s: params, packed, basis, h, c and workspace must be 16-byte aligned", who);
+  if (is_core && (!aligned16(core->core_h) || !aligned16(core->core_c) || !aligned16(core->core_h_out)))
+    return fail(AAA_E_ALIGN, "actor_step_core: core_h, core_c and core_h_out must be 16-byte aligned");
   if ((r = check_device())) return r;
   const char* pk = (const char*)io->packed;
   const float* prm = io->params;
@@ -477,7 +495,7 @@ int aaa_actor_step(const aaa_cfg* cfg, const aaa_actor_io* io, hipStream_t strea
   p.Wp1 = (const float*)(pk + L.k_Wp1); p.b1 = prm + L.poff[C0B];
   p.Wp2 = (const float*)(pk + L.k_Wp2); p.b2 = prm + L.poff[C1B];
   p.WpXH = (const float*)(pk + L.k_WpXH); p.bl = (const float*)(pk + L.k_bl);
-  p.Q = (const float*)(pk + L.k_Q);
+  p.Q = (const float*)(pk + L.k_Q); p.q_stride = 0;
   p.W1p = (const float*)(pk + L.k_W1p); p.a0b = prm + L.poff[A0B];
   p.A2W = prm + L.poff[A2W]; p.a2b = prm + L.poff[A2B];
   p.Wihp = (const float*)(pk + L.k_Wihp); p.blc = (const float*)(pk + L.k_blc);
@@ -490,8 +508,29 @@ int aaa_actor_step(const aaa_cfg* cfg, const aaa_actor_io* io, hipStream_t strea
   p.Zp = (float*)(ws + off[5]); p.zcnt = (int*)(ws + off[6]);
   p.Lg = (float*)(ws + off[7]); p.Apart = (float*)(ws + off[8]); p.arow = (float*)(ws + off[9]);
   p.seed = io->seed; p.counter = io->counter; p.actions = io->actions; p.logp = io->logp; p.jac = io->dlogp_dlogits;
+  p.core_h = p.core_c = p.core_h_out = p.core_c_out = p.query_out = nullptr;
+  p.Q0W = p.Q0B = p.Q2W = p.Q2B = p.Q4W = p.Q4B = p.Wihhp = nullptr;
+  p.Qt = p.q1 = p.q2 = nullptr;
+  if (is_core) {
+    p.core_h = core->core_h; p.core_c = core->core_c; p.core_h_out = core->core_h_out; p.core_c_out = core->core_c_out;
+    p.query_out = core->query;
+    p.Q0W = prm + L.poff[Q0W]; p.Q0B = prm + L.poff[Q0B]; p.Q2W = prm + L.poff[Q2W]; p.Q2B = prm + L.poff[Q2B];
+    p.Q4W = prm + L.poff[Q4W]; p.Q4B = prm + L.poff[Q4B];
+    p.Wihhp = (const float*)(pk + L.k_Wihhp);
+    p.Qt = (float*)(ws + off[10]); p.q1 = (float*)(ws + off[11]); p.q2 = (float*)(ws + off[12]);
+    p.Q = p.Qt; p.q_stride = L.qd;
+  }
   HIPCHK(actor_launch(p, stream));
   return AAA_OK;
+}
+
+int aaa_actor_step(const aaa_cfg* cfg, const aaa_actor_io* io, hipStream_t stream) {
+  return actor_step_impl(cfg, io, nullptr, false, stream);
+}
+
+int aaa_actor_step_core(const aaa_cfg* cfg, const aaa_actor_io* io, const aaa_actor_core_io* core,
+                        hipStream_t stream) {
+  return actor_step_impl(cfg, io, core, true, stream);
 }
 
 }  // extern "C"

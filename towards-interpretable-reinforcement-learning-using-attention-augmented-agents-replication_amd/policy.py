@@ -159,13 +159,16 @@ class Policy(nn.Module):
         return int(action.item())
 
 
-def _actor_chain_fits(B, H, W, nq, A) -> bool:
-    """Whether aaa_actor_step accepts this geometry: its layout query returns 0
-    bytes (AAA_E_ARG) for what it refuses, e.g. a grid whose readout exceeds
-    the kernel's LDS; no device call."""
+def _actor_chain_fits(B, H, W, nq, A, stateful_core: bool = False) -> bool:
+    """Whether aaa_actor_step (aaa_actor_step_core for the stateful policy
+    core) accepts this geometry: its layout query returns 0 bytes (AAA_E_ARG)
+    for what it refuses, e.g. a grid whose readout exceeds the kernel's LDS;
+    no device call."""
     import ctypes
-    cfg = N.Cfg(B, 1, H, W, nq, A, N.F32, N.FLAG_FRAMES_U8)
-    return N.load().aaa_actor_workspace_bytes(ctypes.byref(cfg)) > 0
+    cfg = N.Cfg(B, 1, H, W, nq, A, N.F32, N.FLAG_FRAMES_U8 | (N.FLAG_STATEFUL_CORE if stateful_core else 0))
+    lib = N.load()
+    query = lib.aaa_actor_core_workspace_bytes if stateful_core else lib.aaa_actor_workspace_bytes
+    return query(ctypes.byref(cfg)) > 0
 
 
 class GraphActor:
@@ -178,14 +181,18 @@ class GraphActor:
     Policy.forward, main_mp.py:54-57), with ``logits``, ``values``,
     ``log_prob`` and ``attention`` left in static device buffers.  The
     ConvLSTM state carries between steps inside the graph (``reset()`` zeroes
-    it, attention.py:293-296).  Weights are re-packed into the graph's own
+    it, attention.py:293-296).  For an agent with ``stateful_core`` the policy
+    core's (prev_output, prev_hidden) carry the same way, in ``core_h`` /
+    ``core_c`` (B, 256), and the queries follow them step by step
+    (attention.py:324-331, 356-358).  Weights are re-packed into the graph's own
     buffers whenever a parameter of ``agent`` changed (storage or in-place
     version), so optimizer steps between episodes are picked up.
 
     ``chain`` selects the step: the actor chain (``aaa_actor_step``: six
-    launches sized for small B; fp32 agents with the reference's zero-state
-    policy core, B <= 16) or the learner's T=1 forward (``aaa_forward`` +
-    ``aaa_sample_actions``); None picks the chain whenever it applies.
+    launches sized for small B, or ``aaa_actor_step_core``: seven, for the
+    stateful policy core; fp32 agents, B <= 16) or the learner's T=1 forward
+    (``aaa_forward`` + ``aaa_sample_actions``: bf16 agents, larger B or grids);
+    None picks the chain whenever it applies.
     """
 
     def __init__(self, agent, H: int, W: int, B: int = 1, seed: int = 0, chain: bool | None = None):
@@ -195,14 +202,18 @@ class GraphActor:
         if dev.type != "cuda":
             raise RuntimeError("GraphActor needs the agent on the gfx950 device (there is no CPU fallback)")
         self.device, self.B, self.H, self.W = dev, B, H, W
-        eligible = agent.conv_dtype == "fp32" and not getattr(agent, "stateful_core", False) and B <= 16
+        self.stateful = bool(getattr(agent, "stateful_core", False))
+        eligible = agent.conv_dtype == "fp32" and B <= 16
         if chain and not eligible:
-            raise ValueError("the actor chain needs an fp32 agent with the zero-state policy core and B <= 16")
+            raise ValueError("the actor chain needs an fp32 agent and B <= 16 (bf16 agents and larger batches act "
+                             "through the learner's T=1 forward: chain=False)")
         self.chain = eligible if chain is None else bool(chain)
-        if self.chain and chain is None and not _actor_chain_fits(B, H, W, agent.num_queries, agent.num_actions):
+        if self.chain and chain is None and not _actor_chain_fits(B, H, W, agent.num_queries, agent.num_actions,
+                                                                  self.stateful):
             self.chain = False   # the geometry the chain refuses (its readout LDS): the learner's T=1 forward
         if self.chain:   # any failure here (asked for, or a real HIP error) propagates
-            r = ActorRunner(B, H, W, agent.num_queries, agent.num_actions, dev, frames_u8=True)
+            r = ActorRunner(B, H, W, agent.num_queries, agent.num_actions, dev, frames_u8=True,
+                            stateful_core=self.stateful)
         if self.chain:
             self.runner = r
             self._ws = r.new_workspace()
@@ -214,7 +225,7 @@ class GraphActor:
             self._logp = torch.empty(B, device=dev)
         else:
             r = UnrollRunner(B, 1, H, W, agent.num_queries, agent.num_actions, agent.conv_dtype, dev,
-                             frames_u8=True)
+                             stateful_core=self.stateful, frames_u8=True)
             self.runner = r
         self.S = agent._basis_for(r.h, r.w, H, W, dev)
         self.params = list(agent.parameters())
@@ -224,6 +235,9 @@ class GraphActor:
         self.frame_u8 = torch.zeros(1, B, H, W, 3, dtype=torch.uint8, device=dev)
         self.h = torch.zeros(r.state_shape(), device=dev)
         self.c = torch.zeros(r.state_shape(), device=dev)
+        # the policy core's (prev_output, prev_hidden): carried inside the graph like h / c
+        self.core_h = torch.zeros(B, 256, device=dev) if self.stateful else None
+        self.core_c = torch.zeros(B, 256, device=dev) if self.stateful else None
         self.sampler = ActionSampler(seed, dev)
         self._host = [(torch.empty(B, H, W, 3, dtype=torch.uint8, pin_memory=True), torch.cuda.Event())
                       for _ in range(4)]
@@ -247,15 +261,19 @@ class GraphActor:
             s = self.sampler
             r.step(self.flat, self.packed, self.S, self.frame_u8, self._ws, self.h, self.c, self._logits,
                    self._values, attn=self._attn, seed=s.seed, counter=s.counter, actions=self._actions,
-                   logp=self._logp)
+                   logp=self._logp, core_h=self.core_h, core_c=self.core_c)
             return self._actions, self._logp, self._logits, self._values, self._attn
         X = self.frame_u8                  # uint8, cast in-kernel (AAA_FLAG_FRAMES_U8)
         ws = r.new_workspace()
-        logits, values, attn, hT, cT = r.forward(self.flat, self.packed, self.S, X, ws, h0=self.h, c0=self.c,
-                                                 want_attn=True, want_state=True)
+        out = r.forward(self.flat, self.packed, self.S, X, ws, h0=self.h, c0=self.c, want_attn=True,
+                        want_state=True, core=(self.core_h, self.core_c) if self.stateful else None)
+        logits, values, attn, hT, cT = out[:5]
         action, logp = self.sampler(logits[0])
         self.h.copy_(hT)
         self.c.copy_(cT)
+        if self.stateful:
+            self.core_h.copy_(out[5])
+            self.core_c.copy_(out[6])
         return action, logp, logits[0], values[0], attn[0]
 
     def _refresh(self):
@@ -269,6 +287,9 @@ class GraphActor:
     def reset(self):
         self.h.zero_()
         self.c.zero_()
+        if self.stateful:
+            self.core_h.zero_()
+            self.core_c.zero_()
 
     @property
     def logits(self):

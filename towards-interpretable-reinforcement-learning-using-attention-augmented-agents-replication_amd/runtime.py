@@ -306,24 +306,33 @@ class CnnRunner:
 
 class ActorRunner:
     """One environment step of B <= 16 rows on the actor chain (aaa_actor_step:
-    six launches sized for small B; fp32, zero-state policy core): the acting
+    six launches sized for small B; fp32, zero-state policy core by default): the acting
     half of main_mp.py:49-59 / test_model.py:42-73.  The ConvLSTM state
     tensors ``h``/``c`` (B, h, w, 128) are read and overwritten in place, and
     every output goes to caller-preallocated tensors, so a step can be
-    captured in a HIP graph and replayed."""
+    captured in a HIP graph and replayed.
 
-    def __init__(self, B: int, H: int, W: int, nq: int = 4, A: int = 18, device=None, frames_u8: bool = True):
+    ``stateful_core`` runs the stateful policy core (aaa_actor_step_core, seven
+    launches: the query MLP on ``core_h``, per-row queries in the readout,
+    the LSTMCell from ``(core_h, core_c)``); ``step`` then needs the (B, 256)
+    core state tensors, read and overwritten in place like ``h``/``c``."""
+
+    def __init__(self, B: int, H: int, W: int, nq: int = 4, A: int = 18, device=None, frames_u8: bool = True,
+                 stateful_core: bool = False):
         self.lib = N.load()
         self.device = torch.device(device if device is not None else "cuda")
         if self.device.type != "cuda":
             raise RuntimeError("aaa: the HIP path needs a ROCm GPU tensor device (no CPU fallback)")
         self.B, self.H, self.W, self.nq, self.A = B, H, W, nq, A
         self.frames_u8 = bool(frames_u8)
-        self.cfg = N.Cfg(B, 1, H, W, nq, A, N.F32, N.FLAG_FRAMES_U8 if frames_u8 else 0)
+        self.stateful_core = bool(stateful_core)
+        self.cfg = N.Cfg(B, 1, H, W, nq, A, N.F32, (N.FLAG_FRAMES_U8 if frames_u8 else 0)
+                         | (N.FLAG_STATEFUL_CORE if stateful_core else 0))
         self.h, self.w = N.grid(H, W)
         self.P = self.h * self.w
         self.n_params, self.offsets, self.sizes = N.param_layout(self.cfg)
-        self.ws_bytes = self.lib.aaa_actor_workspace_bytes(ctypes.byref(self.cfg))
+        query = self.lib.aaa_actor_core_workspace_bytes if stateful_core else self.lib.aaa_actor_workspace_bytes
+        self.ws_bytes = query(ctypes.byref(self.cfg))
         self.pk_bytes = self.lib.aaa_packed_bytes(ctypes.byref(self.cfg))
         if not self.ws_bytes or not self.pk_bytes:
             N.check(-1, "actor layout")
@@ -345,11 +354,15 @@ class ActorRunner:
 
     def step(self, flat_params, packed, basis, frames, workspace, h, c, logits, values, attn=None,
              prev_reward=None, prev_action=None, seed: int = 0, counter=None, actions=None, logp=None,
-             dlogp=None, gates=None, h_out=None, c_out=None):
+             dlogp=None, gates=None, h_out=None, c_out=None, core_h=None, core_c=None, core_h_out=None,
+             core_c_out=None, query=None):
         """frames (B, H, W, 3) uint8 (or fp32 without frames_u8); h, c updated in
         place; logits/values (B, A), attn (B, h, w, nq) or None; actions (B,)
         int32 (None: no draw) with logp (B,) / dlogp (B, A) and the device draw
-        ``counter`` (one-element int64, advanced per step) as aaa_sample_actions."""
+        ``counter`` (one-element int64, advanced per step) as aaa_sample_actions.
+        A stateful-core runner also takes core_h, core_c (B, 256), updated in
+        place unless core_h_out / core_c_out are given, and ``query``
+        (B, nq, 72) or None for this step's Q_t."""
         exp = (self.B, self.H, self.W, 3)
         dt = torch.uint8 if self.frames_u8 else torch.float32
         if tuple(frames.shape[-4:]) != exp or frames.numel() != self.B * self.H * self.W * 3 or \
@@ -365,5 +378,23 @@ class ActorRunner:
                          dlogp_dlogits=dlogp, gates=gates, h_out=h_out, c_out=c_out).items():
             setattr(io, k, None if v is None else v.data_ptr())
         io.seed = int(seed) & (2**64 - 1)
-        N.check(self.lib.aaa_actor_step(ctypes.byref(self.cfg), ctypes.byref(io), N.stream_ptr(self.device)),
-                "actor_step")
+        core = dict(core_h=core_h, core_c=core_c, core_h_out=core_h_out, core_c_out=core_c_out)
+        if not self.stateful_core:
+            if query is not None or any(v is not None for v in core.values()):
+                raise ValueError("core_h / core_c / query belong to a stateful_core runner")
+            N.check(self.lib.aaa_actor_step(ctypes.byref(self.cfg), ctypes.byref(io), N.stream_ptr(self.device)),
+                    "actor_step")
+            return
+        if core_h is None or core_c is None:
+            raise ValueError("a stateful_core runner needs core_h and core_c")
+        for name, t in core.items():
+            if t is not None and (tuple(t.shape) != (self.B, 256) or t.dtype != torch.float32 or not t.is_contiguous()):
+                raise ValueError(f"{name} must be contiguous fp32 {(self.B, 256)}")
+        if query is not None and (tuple(query.shape) != (self.B, self.nq, 72) or query.dtype != torch.float32
+                                  or not query.is_contiguous()):
+            raise ValueError(f"query must be contiguous fp32 {(self.B, self.nq, 72)}")
+        cio = N.ActorCoreIO()
+        for k, v in dict(core, query=query).items():
+            setattr(cio, k, None if v is None else v.data_ptr())
+        N.check(self.lib.aaa_actor_step_core(ctypes.byref(self.cfg), ctypes.byref(io), ctypes.byref(cio),
+                                             N.stream_ptr(self.device)), "actor_step_core")
