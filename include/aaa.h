@@ -510,6 +510,47 @@ int aaa_vision_cnn_fwd(const aaa_cnn_desc* d, const float* cnn_params, const voi
 int aaa_vision_cnn_bwd(const aaa_cnn_desc* d, const void* packed, const float* dy2, float* dy1, float* cnn_grads,
                        void* workspace, hipStream_t stream);
 
+/* The bf16 encoder exactly as the learner runs it -- checker entries, not for
+ * a training host.  aaa_vision_cnn_* above converts to fp32 and so never takes
+ * the kernels a bf16 learner step takes (the frame-resident k_vision_fwd, the
+ * banded conv1 / conv2 with a bf16 output, the fused backward
+ * k_vision_bwd_frames); these two call the learner's own dispatch
+ * (vision_fwd<bf16, bf16> and the VISION phase of aaa_backward, with the same
+ * environment selectors: AAA_VIS_FRAMES, AAA_VIS_BAND, AAA_VIS_BWD_FRAMES,
+ * AAA_CONV1_WGRAD_PIPE, AAA_CONV2_WGRAD_PIPE) on caller-owned buffers and hand
+ * back the kernels' raw bf16 products, so a test can evaluate each kernel in
+ * fp64 on that kernel's own operands (tests/vision_bf16_ref.py).
+ *   desc: dtype must be AAA_BF16; flags 0 (fp32 frames) or AAA_FLAG_FRAMES_U8;
+ *         out_ld >= 64 and a multiple of 8 is the row pitch of ``out`` in
+ *         elements (the learner's is 192: the x half of its [x | h] rows).
+ *   packed: aaa_vision_cnn_pack with an aaa_cnn_desc of the same N, H, W and
+ *         AAA_BF16 (the layouts are the same).
+ *   fwd:  frames (N,H,W,3) -> xp (N,H+2,W+2,4) bf16 the zero-bordered RGBx
+ *         frames (the banded conv1 writes the rows conv1 reads, 0 .. 4*H1+3,
+ *         and leaves any below them alone), y1 (N,H1*W1,32) bf16 conv1's output, out (N,h*w,out_ld)
+ *         bf16 conv2's output in columns 0..63 (the others are not written).
+ *   bwd:  frames, dy2 (N,h*w,64) bf16, y1 and xp of the forward -> cnn_grads
+ *         (39,008 fp32, cnn_params' layout, overwritten; conv2's bias gradient
+ *         is the column sum of dy2), *fused (host int, may be NULL) = 1 when
+ *         k_vision_bwd_frames ran, 0 for the layered launches, which also
+ *         write dy1 (N,H1*W1,32) bf16 (the fused kernel keeps it on chip and
+ *         leaves dy1 alone).  The workspace lends the fused kernel's partials
+ *         their room, so -- unlike a learner step, which takes it from the
+ *         frames' dY1 region and so needs about 7 frames -- any N may fuse.
+ * Launches are recorded under AAA_TIMER_VISION_FWD / _BWD with the learner's
+ * variant strings.  Arguments are checked before the device (a refusal needs
+ * no GPU); every pointer 16-byte aligned.  Added after ABI version 11 without
+ * a bump (purely additive): probe by name. */
+typedef struct aaa_enc_desc {
+  int N, H, W, dtype, flags, out_ld;
+} aaa_enc_desc;
+size_t aaa_vision_enc_workspace_bytes(const aaa_enc_desc* d);
+int aaa_vision_enc_fwd(const aaa_enc_desc* d, const float* cnn_params, const void* packed, const void* frames,
+                       void* xp, void* y1, void* out, hipStream_t stream);
+int aaa_vision_enc_bwd(const aaa_enc_desc* d, const void* packed, const void* frames, const void* dy2,
+                       const void* y1, void* xp, void* dy1, float* cnn_grads, int* fused, void* workspace,
+                       hipStream_t stream);
+
 /* Attention readout of F frames (attention.py:319-348: K/V split + spatial
  * basis, logits K.Q, spatial_softmax :235-243, apply_alpha :246-254, answer
  * assembly): O (F,h,w,128) the vision output, S (h,w,64), Q (nq,72) shared by

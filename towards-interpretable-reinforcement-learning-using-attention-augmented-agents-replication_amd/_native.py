@@ -34,6 +34,7 @@ EXPORTS = (
     "aaa_core_elem_bytes", "aaa_forward_phases", "aaa_core_export", "aaa_core_import",
     # added after ABI 11 without a bump (purely additive; include/aaa.h): probed by name
     "aaa_actor_core_workspace_bytes", "aaa_actor_step_core",
+    "aaa_vision_enc_workspace_bytes", "aaa_vision_enc_fwd", "aaa_vision_enc_bwd",
 )
 # include/aaa.h enum aaa_timer
 TIMER_FWD_STEP, TIMER_BPTT_STEP, TIMER_CORE_WGRAD, TIMER_ATTN_FWD, TIMER_ATTN_BWD = 0, 1, 2, 3, 4
@@ -95,6 +96,11 @@ class CellDesc(ctypes.Structure):
 
 class CnnDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int) for n in ("N", "H", "W", "dtype")]
+
+
+class EncDesc(ctypes.Structure):
+    """include/aaa.h aaa_enc_desc (aaa_vision_enc_*: the learner's bf16 encoder kernels, checker entries)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("N", "H", "W", "dtype", "flags", "out_ld")]
 
 
 class ConvDesc(ctypes.Structure):
@@ -164,6 +170,9 @@ def load(path: str = LIB_PATH):
             "aaa_vision_cnn_pack": (I, [ctypes.POINTER(CnnDesc), P, P, P]),
             "aaa_vision_cnn_fwd": (I, [ctypes.POINTER(CnnDesc), P, P, P, P, P, P, P]),
             "aaa_vision_cnn_bwd": (I, [ctypes.POINTER(CnnDesc), P, P, P, P, P, P]),
+            "aaa_vision_enc_workspace_bytes": (S, [ctypes.POINTER(EncDesc)]),
+            "aaa_vision_enc_fwd": (I, [ctypes.POINTER(EncDesc), P, P, P, P, P, P, P]),
+            "aaa_vision_enc_bwd": (I, [ctypes.POINTER(EncDesc), P, P, P, P, P, P, P, ctypes.POINTER(I), P, P]),
             "aaa_attn_fwd": (I, [I, I, I, I, P, P, P, I, P, P, P, P, P]),
             "aaa_attn_bwd": (I, [I, I, I, I, P, P, P, I, P, P, P, P, P]),
             "aaa_attn_fwd_bf16": (I, [I, I, I, I, P, I, P, P, I, P, P, P, P, P, P]),

@@ -51,7 +51,12 @@ int fail(int code, const char* fmt, ...);
 
 inline size_t al256(size_t x) { return (x + 255) & ~size_t(255); }
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
-inline int conv_out(int n, int k, int s, int p) { return (n + 2 * p - k) / s + 1; }
+// (0 when the padded input is smaller than the kernel: C's division truncates toward zero, and
+// (n + 2p - k) / s + 1 would call a 4x4 frame a 1x1 conv1 map whose 8x8 window is not there)
+inline int conv_out(int n, int k, int s, int p) {
+  const int d = n + 2 * p - k;
+  return d < 0 ? 0 : d / s + 1;
+}
 
 enum PIdx {
   C0W = 0, C0B, C1W, C1B,
@@ -611,13 +616,19 @@ bool f32_split6();
 template <typename T> int pack_impl(const Layout& L, const float* prm, char* pk, hipStream_t st);
 template <typename T, typename OT>
 int vision_fwd(const Layout& L, int F, const char* pk, const float* prm, const void* frames, T* Xp, T* Y1, OT* out,
-               int out_ld, hipStream_t st, bool xp_full = true);
+               int out_ld, hipStream_t st, bool xp_full = true, std::string* ran = nullptr);   // ran <- the kernels taken
 template <typename T> int forward_impl(const Layout& L, const aaa_io* io, hipStream_t st, int phases);
 template <typename T>
 int lstm_wgrad(const T* dz, const T* xh, int rows, int h, int w, float* gW, hipStream_t s, bool aux);
 template <typename T>
 int vision_bwd(const Layout& L, const char* pk, const T* dy2, const T* y1, T* xp, T* dy1, int F, float* gW2,
                float* gW1, float* gb1, hipStream_t s, const void* frames = nullptr);
+// backward_impl's VISION phase on its own (rt_backward.hip), shared with aaa_vision_enc_bwd
+const char* vision_bwd_variant(bool fused);
+template <typename T>
+int vision_bwd_alone(const Layout& L, const char* pk, const void* frames, const T* dy2, const T* y1, T* xp, T* dy1,
+                     void* part, size_t part_bytes, int F, float* gW2, float* gW1, float* gb1, hipStream_t st,
+                     const void* xp_frames, bool* fused);
 template <typename T> int backward_impl(const Layout& L, const aaa_io* io, int phases, hipStream_t st);
 
 }  // namespace aaa

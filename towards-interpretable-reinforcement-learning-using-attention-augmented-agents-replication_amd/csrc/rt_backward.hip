@@ -112,7 +112,7 @@ static int conv2_wgrad(const Layout& L, const T* dy2, const T* y1, int frames, f
     // tiles of 4 waves, split-K over about one wave of workgroups, atomics from the accumulators
     // default 1 (C3 1.063M -> 1.075M frames/s, C5 277.4k -> 279.0k vs the register-staged GEMM;
     // 2 = the read-ahead ring, slower here: profiles/r03/ab/convwgrad/); 0 = register-staged
-    const int pipe = ab_int("AAA_CONV2_WGRAD_PIPE", 1);
+    const int pipe = env_int("AAA_CONV2_WGRAD_PIPE", 1);
     if (rows % 32 == 0 && pipe) {
       using CW = GemmCfg<T, 64, 256, 32, 1, 4>;
       using PA = GRowsT<T, CW::BI, CW::BK, CW::NT>;
@@ -190,7 +190,7 @@ static int conv1_wgrad(const Layout& L, const T* dy1, const T* xp, int frames, f
     // waves over all (tap, channel) columns, BK = 64 pixels; a 16-B piece = 2 taps x 4 channels,
     // contiguous in the bordered RGBx image (KW = 8 even, pad 0: every piece in bounds)
     // default 1 (C3 +0.5 %, C5 +0.8 % vs the register-staged GEMM: profiles/r03/ab/convwgrad/)
-    const int pipe = ab_int("AAA_CONV1_WGRAD_PIPE", 1);
+    const int pipe = env_int("AAA_CONV1_WGRAD_PIPE", 1);
     if (rows1 % 64 == 0 && pipe) {
       using CW = GemmCfg<T, 32, 256, 64, 1, 4>;
       using PA = GRowsT<T, CW::BI, CW::BK, CW::NT>;
@@ -467,15 +467,17 @@ int vision_bwd(const Layout& L, const char* pk, const T* dy2, const T* y1, T* xp
 // layered launches above; AAA_VBWD_MINF: a frames-per-CU floor, 0 by default -- with the partial
 // sums reduced 4 waves per 64 columns the fused kernel's fixed cost is ~30 us, below the layered
 // launches' own: C3 (20 frames per CU) 281 vs 358 us, C4 (10) 155 vs 199 us).
+// part_bytes: the room the caller lends the partials (0: the F frames' dY1 region, as the learner does).
 template <typename T>
-static bool vbwd_on(const Layout& L, int F) {
+static bool vbwd_on(const Layout& L, int F, size_t part_bytes = 0) {
   if constexpr (!std::is_same<T, __bf16>::value) {
-    (void)L; (void)F;
+    (void)L; (void)F; (void)part_bytes;
     return false;
   } else {
+    if (!part_bytes) part_bytes = (size_t)F * L.P1 * 32 * L.esz;
     return L.fu8 && vbwd_fits(L.H, L.W, L.H1, L.W1, L.h, L.w) && env_int("AAA_VIS_FRAMES", 1) &&
            env_int("AAA_VIS_BWD_FRAMES", 1) && F >= env_int("AAA_VBWD_MINF", 0) * device_cus() &&
-           (size_t)vbwd_groups(F, device_cus()) * kVbPart * 4 <= (size_t)F * L.P1 * 32 * L.esz;
+           (size_t)vbwd_groups(F, device_cus()) * kVbPart * 4 <= part_bytes;
   }
 }
 // F frames from ``f0``: conv2 wgrad (gW2 +=), conv2 dgrad + conv1 wgrad (gW1 +=, conv1 bias gb1 +=),
@@ -491,6 +493,30 @@ static int vbwd_run(const Layout& L, const char* pk, const void* frames, int f0,
     HIPCHK(vision_bwd_frames(vp, device_cus(), gW2, gW1, gb1, s));
     return AAA_OK;
   }
+}
+
+// The VISION phase on its own (backward_impl without CORE in the same call, and the encoder checker
+// entry aaa_vision_enc_bwd): the frame-resident launch when vbwd_on says so (its partials in ``part``,
+// part_bytes of room; 0 = dy1, the F frames' dY1 region), else the layered launches over all F frames
+// (xp_frames: the observation the Xp chunk buffer is rebuilt from, null = xp holds every frame).
+// Accumulators zeroed by the caller; *fused (may be null) <- which of the two ran.
+const char* vision_bwd_variant(bool fused) {
+  return fused ? "frame-resident conv2 wgrad + dgrad + conv1 wgrad [kernel: k_vision_bwd_frames], grad unpack"
+               : "conv2 wgrad + dgrad, conv1 wgrad, grad unpack";
+}
+template <typename T>
+int vision_bwd_alone(const Layout& L, const char* pk, const void* frames, const T* dy2, const T* y1, T* xp, T* dy1,
+                     void* part, size_t part_bytes, int F, float* gW2, float* gW1, float* gb1, hipStream_t st,
+                     const void* xp_frames, bool* fused) {
+  const bool on = vbwd_on<T>(L, F, part_bytes);
+  if (fused) *fused = on;
+  if (on) return vbwd_run<T>(L, pk, frames, 0, F, dy2, y1, part ? (T*)part : dy1, gW2, gW1, gb1, st);
+  const int rc = vision_bwd<T>(L, pk, dy2, y1, xp, dy1, F, gW2, gW1, gb1, st, xp_frames);
+  if (rc) return rc;
+  // fp32 with AAA_CONV2_DGRAD_RING=0: conv1's bias gradient by a column sum
+  if (std::is_same<T, float>::value && !ab_int("AAA_CONV2_DGRAD_RING", 1))
+    HIPCHK(colsum(dy1, 32, F * L.P1, 32, gb1, st));
+  return AAA_OK;
 }
 
 // ------------------------------------------------------------ backward ----
@@ -744,30 +770,19 @@ int backward_impl(const Layout& L, const aaa_io* io, int phases, hipStream_t st)
     auto vision = [&](hipStream_t vs) -> int {
       const T* dy2 = Wt(L.dY2) + (size_t)lo * M * 64;
       T* dy1 = Wt(L.dY1) + (size_t)lo * L.B * L.P1 * 32;
-      if (vbwd_on<T>(L, F1)) {   // one frame-resident launch (+ its partials' sum)
-        TimerScope tim(AAA_TIMER_VISION_BWD, vs, (double)F1 * vision_bwd_flop(L),
-                       "frame-resident conv2 wgrad + dgrad + conv1 wgrad [kernel: k_vision_bwd_frames]");
-        return vbwd_run<T>(L, pk, io->frames, lo * L.B, F1, dy2, Wt(L.Y1) + (size_t)lo * L.B * L.P1 * 32, dy1,
-                           Wf(L.gWp2), Wf(L.gWp1), grads + L.poff[C0B], vs);
-      }
-      TimerScope tim(AAA_TIMER_VISION_BWD, vs, (double)F1 * vision_bwd_flop(L), "conv2 wgrad + dgrad, conv1 wgrad");
-      const int rows1 = F1 * L.P1;
-      constexpr bool f32 = std::is_same<T, float>::value;   // fp32 with AAA_CONV2_DGRAD_RING=0: conv1 bias by a column sum
-      {  // conv2 wgrad
-        const int rc = conv2_wgrad<T>(L, dy2, Wt(L.Y1) + (size_t)lo * L.B * L.P1 * 32, F1, Wf(L.gWp2), vs);
-        if (rc) return rc;
-      }
-      {  // conv2 dgrad (4 parity classes) -> dY1, then conv1 wgrad / bias
-        int rc = conv2_dgrad<T>(L, pk, dy2, dy1, F1, grads + L.poff[C0B], vs);
-        if (!rc && L.xpc < L.F)   // Xp chunk buffer: rebuilt from the observation
-          rc = conv1_wgrad_frames<T>(L, dy1, (const char*)io->frames + (size_t)lo * L.B * L.H * L.W * 3 * (L.fu8 ? 1 : 4),
-                                     F1, Wt(L.Xp), Wf(L.gWp1), vs);
-        else if (!rc)
-          rc = conv1_wgrad<T>(L, dy1, Wt(L.Xp) + (size_t)lo * L.B * (L.H + 2) * (L.W + 2) * 4, F1, Wf(L.gWp1), vs);
-        if (rc) return rc;
-        if (f32 && !ab_int("AAA_CONV2_DGRAD_RING", 1)) HIPCHK(colsum(dy1, 32, rows1, 32, grads + L.poff[C0B], vs));
-      }
-      return AAA_OK;
+      // one frame-resident launch (+ its partials' sum), or conv2 wgrad, conv2 dgrad (4 parity classes) -> dY1,
+      // conv1 wgrad / bias: the dispatch of the VISION phase on its own (vision_bwd_alone), on this chunk's frames
+      // (a chunk is at most L.fchunk frames: one pass of its loop)
+      const bool on = vbwd_on<T>(L, F1);
+      TimerScope tim(AAA_TIMER_VISION_BWD, vs, (double)F1 * vision_bwd_flop(L),
+                     on ? "frame-resident conv2 wgrad + dgrad + conv1 wgrad [kernel: k_vision_bwd_frames]"
+                        : "conv2 wgrad + dgrad, conv1 wgrad");
+      const void* fr = (const char*)io->frames + (size_t)lo * L.B * L.H * L.W * 3 * (L.fu8 ? 1 : 4);
+      const bool chunked = L.xpc < L.F;   // Xp chunk buffer: rebuilt from the observation
+      return vision_bwd_alone<T>(L, pk, fr, dy2, Wt(L.Y1) + (size_t)lo * L.B * L.P1 * 32,
+                                 chunked ? Wt(L.Xp) : Wt(L.Xp) + (size_t)lo * L.B * (L.H + 2) * (L.W + 2) * 4, dy1,
+                                 nullptr, 0, F1, Wf(L.gWp2), Wf(L.gWp1), grads + L.poff[C0B], vs,
+                                 chunked ? fr : nullptr, nullptr);
     };
     // (the layered vision backward on the side stream beside the ConvLSTM weight gradient, ablation
     // builds with AAA_VIS_SIDE=1: C2 232.0k -> 228.6-229.2k, C5 within noise -- the two contend for
@@ -1202,22 +1217,12 @@ int backward_impl(const Layout& L, const aaa_io* io, int phases, hipStream_t st)
 
   if (phases & AAA_BWD_VISION) {
     TimerScope tim(AAA_TIMER_VISION_BWD, st, vision_here ? 0.0 : (double)F * vision_bwd_flop(L),
-                   vbwd_on<T>(L, F) ? "frame-resident conv2 wgrad + dgrad + conv1 wgrad [kernel: k_vision_bwd_frames], "
-                                      "grad unpack"
-                                    : "conv2 wgrad + dgrad, conv1 wgrad, grad unpack");
-    if (!vision_here && vbwd_on<T>(L, F)) {   // VISION alone, frame-resident
-      const int rc = vbwd_run<T>(L, pk, io->frames, 0, F, Wt(L.dY2), Wt(L.Y1), Wt(L.dY1), Wf(L.gWp2), Wf(L.gWp1),
-                                 grads + L.poff[C0B], st);
+                   vision_bwd_variant(vbwd_on<T>(L, F)));
+    if (!vision_here) {   // VISION alone: frame-resident, or its chunk work over all frames, here
+      const int rc = vision_bwd_alone<T>(L, pk, io->frames, Wt(L.dY2), Wt(L.Y1), Wt(L.Xp), Wt(L.dY1), nullptr, 0, F,
+                                         Wf(L.gWp2), Wf(L.gWp1), grads + L.poff[C0B], st,
+                                         L.xpc < L.F ? io->frames : nullptr, nullptr);
       if (rc) return rc;
-    } else if (!vision_here) {   // VISION alone: its chunk work over all frames, here
-      const int rows1 = F * L.P1;
-      constexpr bool f32 = std::is_same<T, float>::value;
-      {
-        const int rc = vision_bwd<T>(L, pk, Wt(L.dY2), Wt(L.Y1), Wt(L.Xp), Wt(L.dY1), F, Wf(L.gWp2), Wf(L.gWp1),
-                                     grads + L.poff[C0B], st, L.xpc < L.F ? io->frames : nullptr);
-        if (rc) return rc;
-        if (f32 && !ab_int("AAA_CONV2_DGRAD_RING", 1)) HIPCHK(colsum(Wt(L.dY1), 32, rows1, 32, grads + L.poff[C0B], st));
-      }
     }
     HIPCHK(unpack_cv((phases & AAA_BWD_CORE) ? Wf(L.gWpl) : nullptr, Wf(L.gbl), core_unpack, Wf(L.gWp2),
                      grads + L.poff[C1W], Wf(L.gWp1), grads + L.poff[C0W], st));
@@ -1232,6 +1237,12 @@ template int vision_bwd<float>(const Layout&, const char*, const float*, const f
                                float*, float*, float*, hipStream_t, const void*);
 template int vision_bwd<__bf16>(const Layout&, const char*, const __bf16*, const __bf16*, __bf16*, __bf16*, int,
                                 float*, float*, float*, hipStream_t, const void*);
+template int vision_bwd_alone<float>(const Layout&, const char*, const void*, const float*, const float*, float*,
+                                     float*, void*, size_t, int, float*, float*, float*, hipStream_t, const void*,
+                                     bool*);
+template int vision_bwd_alone<__bf16>(const Layout&, const char*, const void*, const __bf16*, const __bf16*, __bf16*,
+                                      __bf16*, void*, size_t, int, float*, float*, float*, hipStream_t, const void*,
+                                      bool*);
 template int backward_impl<float>(const Layout&, const aaa_io*, int, hipStream_t);
 template int backward_impl<__bf16>(const Layout&, const aaa_io*, int, hipStream_t);
 

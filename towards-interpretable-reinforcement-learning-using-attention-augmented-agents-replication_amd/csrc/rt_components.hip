@@ -199,6 +199,39 @@ static int cnn_bwd_impl(const CnnLayout& CL, const char* pk, const float* dy2, f
   return AAA_OK;
 }
 
+// The learner's own bf16 encoder kernels over N frames (checker entries aaa_vision_enc_*): a Layout
+// with B = N, T = 1 whose fu8 follows the flag, so vision_fwd<__bf16, __bf16> and the VISION phase's
+// dispatch (vision_bwd_alone) choose as they do inside a learner step.  Every product is a
+// caller-owned buffer; the workspace holds the packed-gradient accumulators and the fused
+// backward's per-workgroup partials (one per 8 frames at the most, vbwd_groups).
+struct EncLayout {
+  Layout L;
+  size_t gW1, gW2, part, part_bytes, ws;
+};
+
+static int enc_layout(const aaa_enc_desc* d, EncLayout& E) {
+  if (!d) return fail(AAA_E_ARG, "enc desc is NULL");
+  if (d->dtype != AAA_BF16) return fail(AAA_E_ARG, "vision_enc: bf16 only (dtype %d)", d->dtype);
+  if (d->N < 1) return fail(AAA_E_ARG, "vision_enc: need N >= 1");
+  if (d->flags & ~AAA_FLAG_FRAMES_U8) return fail(AAA_E_ARG, "vision_enc: flags may hold AAA_FLAG_FRAMES_U8 only");
+  if (d->out_ld < 64 || d->out_ld % 8)
+    return fail(AAA_E_ARG, "vision_enc: out_ld must be >= 64 and a multiple of 8 (got %d)", d->out_ld);
+  const aaa_cfg cfg{d->N, 1, d->H, d->W, 4, 18, d->dtype, d->flags};
+  int r = build_layout(&cfg, E.L, 1);
+  if (r) return r;
+  const Layout& L = E.L;
+  if ((size_t)L.F * L.P * d->out_ld * 2 >= (size_t(1) << 31))
+    return fail(AAA_E_ARG, "vision_enc: N*h*w*out_ld is above the 2 GiB descriptor range; split N");
+  size_t p = 0;
+  auto take = [&](size_t bytes) { size_t q = p; p = al256(p + bytes); return q; };
+  E.gW1 = take(32 * 256 * 4);
+  E.gW2 = take(64 * 512 * 4);
+  E.part_bytes = (size_t)std::max(1, L.F / 8) * kVbPart * 4;
+  E.part = take(E.part_bytes);
+  E.ws = p;
+  return AAA_OK;
+}
+
 // ----------------------------------------------------- unit-test entries --
 template <typename T>
 static int conv_nhwc_impl(const aaa_conv_desc* d, const float* x, const float* w, const float* bias, float* y,
@@ -439,6 +472,67 @@ int aaa_vision_cnn_bwd(const aaa_cnn_desc* d, const void* packed, const float* d
   return C.L.dt == AAA_BF16
              ? cnn_bwd_impl<__bf16>(C, (const char*)packed, dy2, dy1, cnn_grads, (char*)workspace, stream)
              : cnn_bwd_impl<float>(C, (const char*)packed, dy2, dy1, cnn_grads, (char*)workspace, stream);
+}
+
+// ---- the bf16 encoder as the learner runs it (checker entries; arguments checked before the device) ----
+size_t aaa_vision_enc_workspace_bytes(const aaa_enc_desc* d) {
+  EncLayout E;
+  return enc_layout(d, E) ? 0 : E.ws;
+}
+
+int aaa_vision_enc_fwd(const aaa_enc_desc* d, const float* cnn_params, const void* packed, const void* frames,
+                       void* xp, void* y1, void* out, hipStream_t stream) {
+  EncLayout E;
+  int r = enc_layout(d, E);
+  if (r) return r;
+  if (!cnn_params || !packed || !frames || !xp || !y1 || !out)
+    return fail(AAA_E_ARG, "vision_enc_fwd: cnn_params/packed/frames/xp/y1/out must be set");
+  const void* ptrs[] = {cnn_params, packed, frames, xp, y1, out};
+  for (const void* p : ptrs)
+    if (!aligned16(p)) return fail(AAA_E_ALIGN, "buffers must be 16-byte aligned");
+  if ((r = check_device())) return r;
+  const Layout& L = E.L;
+  TimerScope tim(AAA_TIMER_VISION_FWD, stream, (double)L.F * vision_fwd_flop(L), "conv1 + conv2 (vision encoder)");
+  std::string ran;
+  r = vision_fwd<__bf16, __bf16>(L, L.F, (const char*)packed, cnn_params, frames, (__bf16*)xp, (__bf16*)y1,
+                                 (__bf16*)out, d->out_ld, stream, true, &ran);
+  tim.variant += ": " + ran;
+  return r;
+}
+
+int aaa_vision_enc_bwd(const aaa_enc_desc* d, const void* packed, const void* frames, const void* dy2,
+                       const void* y1, void* xp, void* dy1, float* cnn_grads, int* fused, void* workspace,
+                       hipStream_t stream) {
+  EncLayout E;
+  int r = enc_layout(d, E);
+  if (r) return r;
+  if (!packed || !frames || !dy2 || !y1 || !xp || !dy1 || !cnn_grads || !workspace)
+    return fail(AAA_E_ARG, "vision_enc_bwd: packed/frames/dy2/y1/xp/dy1/cnn_grads/workspace must be set");
+  const void* ptrs[] = {packed, frames, dy2, y1, xp, dy1, cnn_grads, workspace};
+  for (const void* p : ptrs)
+    if (!aligned16(p)) return fail(AAA_E_ALIGN, "buffers must be 16-byte aligned");
+  if ((r = check_device())) return r;
+  const Layout& L = E.L;
+  char* ws = (char*)workspace;
+  float* gW1 = (float*)(ws + E.gW1);
+  float* gW2 = (float*)(ws + E.gW2);
+  HIPCHK(hipMemsetAsync(cnn_grads, 0, L.poff[XI_W] * 4, stream));
+  HIPCHK(hipMemsetAsync(gW1, 0, 32 * 256 * 4, stream));
+  HIPCHK(hipMemsetAsync(gW2, 0, 64 * 512 * 4, stream));
+  // conv2's bias gradient: the learner sums it where dY2 is produced (the ConvLSTM dx epilogue); here from dY2
+  HIPCHK(colsum<__bf16>((const __bf16*)dy2, 64, L.F * L.P, 64, cnn_grads + L.poff[C1B], stream));
+  bool on = false;
+  {
+    TimerScope tim(AAA_TIMER_VISION_BWD, stream, (double)L.F * vision_bwd_flop(L), "");
+    r = vision_bwd_alone<__bf16>(L, (const char*)packed, frames, (const __bf16*)dy2, (const __bf16*)y1, (__bf16*)xp,
+                                 (__bf16*)dy1, ws + E.part, E.part_bytes, L.F, gW2, gW1, cnn_grads + L.poff[C0B],
+                                 stream, nullptr, &on);
+    tim.variant = vision_bwd_variant(on);
+    if (r) return r;
+    HIPCHK(unpack_cv(nullptr, nullptr, LstmGrads{}, gW2, cnn_grads + L.poff[C1W], gW1, cnn_grads + L.poff[C0W], stream));
+  }
+  if (fused) *fused = on ? 1 : 0;
+  return AAA_OK;
 }
 
 static int check_attn_args(int F, int h, int w, int nq, int q_stride) {

@@ -54,13 +54,13 @@ int pack_impl(const Layout& L, const float* prm, char* pk, hipStream_t st) {
 // from the flat params (state_dict order: the vision tensors come first).
 template <typename T, typename OT>
 static int vision_fwd_chunk(const Layout& L, int F, const char* pk, const float* prm, const void* frames, T* Xp, T* Y1,
-                      OT* out, int out_ld, hipStream_t st, bool xp_full) {
+                      OT* out, int out_ld, hipStream_t st, bool xp_full, std::string* ran) {
   using C = CfgFor<T>;
   constexpr int NT = C::NT;
   const int P = L.P;
   bool banded = false;   // bf16 frames too large for the frame-resident encoder: the banded conv1 (vision.h)
   if constexpr (std::is_same<T, __bf16>::value) {
-    if (band_fits(L.H, L.W, L.H1, L.W1) && ab_int("AAA_VIS_BAND", 1)) {
+    if (band_fits(L.H, L.W, L.H1, L.W1) && env_int("AAA_VIS_BAND", 1)) {
       const VisBandParams bp{frames, (const __bf16*)(pk + L.k_Wp1), prm + L.poff[C0B], xp_full ? Xp : nullptr, Y1, F,
                              L.H, L.W, L.H1, L.W1};
       HIPCHK(L.fu8 ? vision_conv1_band<uint8_t>(bp, st) : vision_conv1_band<float>(bp, st));
@@ -111,6 +111,7 @@ static int vision_fwd_chunk(const Layout& L, int F, const char* pk, const float*
     if (banded && band2_fits(L.H1, L.W1, L.h, L.w) && ab_int("AAA_VIS_BAND2", 1)) {
       const VisBand2Params bp{Y1, (const __bf16*)(pk + L.k_Wp2), prm + L.poff[C1B], out, out_ld, F, L.H1, L.W1, L.h, L.w};
       HIPCHK(vision_conv2_band(bp, st));
+      if (ran) *ran = "banded conv1 [kernel: k_vision_conv1_band], banded conv2 [kernel: k_vision_conv2_band]";
       return AAA_OK;
     }
   }
@@ -134,19 +135,23 @@ static int vision_fwd_chunk(const Layout& L, int F, const char* pk, const float*
       HIPCHK((launch_gemm<C, LA, LB>(pa, typename LB::Params{Y1, g, F * P}, ep, 64, F * P, 512, 1, st)));
     }
   }
+  if (ran)
+    *ran = banded ? "banded conv1 [kernel: k_vision_conv1_band], conv2 im2col GEMM"
+                  : "layered: frames_rgbx, conv1 im2col ring, conv2 im2col GEMM";
   return AAA_OK;
 }
 
 
 template <typename T, typename OT>
 int vision_fwd(const Layout& L, int F, const char* pk, const float* prm, const void* frames, T* Xp, T* Y1,
-                      OT* out, int out_ld, hipStream_t st, bool xp_full) {
+                      OT* out, int out_ld, hipStream_t st, bool xp_full, std::string* ran) {
   if constexpr (std::is_same<T, __bf16>::value && std::is_same<OT, __bf16>::value) {
     // bf16: the frame-resident encoder (vision.h), one launch; AAA_VIS_FRAMES=0 -> the layered kernels
     if (vis_fits(L.H, L.W, L.H1, L.W1, L.h, L.w) && env_int("AAA_VIS_FRAMES", 1)) {
       VisFwdParams vp{frames, (const __bf16*)(pk + L.k_Wp1), prm + L.poff[C0B], (const __bf16*)(pk + L.k_Wp2),
                       prm + L.poff[C1B], xp_full ? Xp : nullptr, Y1, out, out_ld, F, L.H, L.W, L.H1, L.W1, L.h, L.w};
       HIPCHK(L.fu8 ? vision_fwd_frames<uint8_t>(vp, device_cus(), st) : vision_fwd_frames<float>(vp, device_cus(), st));
+      if (ran) *ran = "frame-resident conv1 + conv2 [kernel: k_vision_fwd]";
       return AAA_OK;
     }
   }
@@ -156,7 +161,7 @@ int vision_fwd(const Layout& L, int F, const char* pk, const float* prm, const v
                                            (const char*)frames + (size_t)f0 * L.H * L.W * 3 * (L.fu8 ? 1 : 4),
                                            xp_full ? Xp + (size_t)f0 * (L.H + 2) * (L.W + 2) * 4 : Xp,
                                            Y1 + (size_t)f0 * L.P1 * 32, out + (size_t)f0 * L.P * out_ld, out_ld, st,
-                                           xp_full);
+                                           xp_full, ran);
     if (rc) return rc;
   }
   return AAA_OK;
@@ -182,8 +187,10 @@ int forward_impl(const Layout& L, const aaa_io* io, hipStream_t st, int phases) 
 
   {  // conv1 + conv2 over all T*B frames -> XH[:, :, 0:64] of every slot
     TimerScope tim(AAA_TIMER_VISION_FWD, st, (double)F * vision_fwd_flop(L), "conv1 + conv2 (vision encoder)");
-    const int rc = vision_fwd<T, T>(L, F, pk, prm, io->frames, Wt(L.Xp), Wt(L.Y1), Wt(L.XH), 192, st, L.xpc >= F);
+    std::string ran;   // the kernels the dispatch took, for the timer's variant
+    const int rc = vision_fwd<T, T>(L, F, pk, prm, io->frames, Wt(L.Xp), Wt(L.Y1), Wt(L.XH), 192, st, L.xpc >= F, &ran);
     if (rc) return rc;
+    tim.variant += ": " + ran;
   }
   {  // initial state (reset(): zeros, attention.py:142-149) or carried state
     TimerScope tim(AAA_TIMER_MISC, st, 0.0, "state in/out copies, memsets, bias column sums");
@@ -533,11 +540,11 @@ static int forward_tail(const Layout& L, const aaa_io* io, hipStream_t st) {
 template int pack_impl<float>(const Layout&, const float*, char*, hipStream_t);
 template int pack_impl<__bf16>(const Layout&, const float*, char*, hipStream_t);
 template int vision_fwd<float, float>(const Layout&, int, const char*, const float*, const void*, float*, float*,
-                                      float*, int, hipStream_t, bool);
+                                      float*, int, hipStream_t, bool, std::string*);
 template int vision_fwd<__bf16, __bf16>(const Layout&, int, const char*, const float*, const void*, __bf16*, __bf16*,
-                                        __bf16*, int, hipStream_t, bool);
+                                        __bf16*, int, hipStream_t, bool, std::string*);
 template int vision_fwd<__bf16, float>(const Layout&, int, const char*, const float*, const void*, __bf16*, __bf16*,
-                                       float*, int, hipStream_t, bool);
+                                       float*, int, hipStream_t, bool, std::string*);
 template int forward_impl<float>(const Layout&, const aaa_io*, hipStream_t, int);
 template int forward_impl<__bf16>(const Layout&, const aaa_io*, hipStream_t, int);
 
