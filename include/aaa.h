@@ -352,6 +352,50 @@ int aaa_adam_step_counted(const aaa_adam_hparams* hp, int* step_dev, const float
 int aaa_reinforce(int T, int B, int A, const float* logits, const int* actions, const float* rewards, double gamma,
                   float* loss, float* returns_norm, float* dlogits, hipStream_t stream);
 
+/* ---- V-trace actor-critic loss (added after ABI 11 without a bump: additive, probe by name) ----
+ * The IMPALA loss for B unrolls of T steps cut out of longer episodes, on
+ * device, in one launch: from the unroll's logits l and values v (T, B, A),
+ * the actions a taken, the rewards r and the behaviour policy's log-probs
+ * log mu of those actions (aaa_actor_step's logp), the cotangents dlogits and
+ * dvalues (T, B, A) that aaa_backward takes.  The baseline is one column of
+ * the A-wide value head, V_t = v[t][b][value_col]; every other column gets a
+ * zero cotangent.  With log pi_t = log_softmax(l_t) (fp32, no clamp), p its
+ * softmax and H_t = -sum_k p_k log pi_k:
+ *   log rho_t = log pi_t[a_t] - log mu_t              (0 when behaviour_logp is NULL)
+ *   rho_t = min(rho_bar, e^{log rho_t}),  c_t = lambda min(c_bar, e^{log rho_t}),
+ *   rho^pg_t = min(pg_rho_bar, e^{log rho_t})
+ *   gamma_t = gamma (1 - [done_t != 0])               (done_t: the episode ended with step t's transition)
+ *   V_T = bootstrap[b]                                (0 when bootstrap is NULL)
+ *   delta_t = rho_t (r_t + gamma_t V_{t+1} - V_t)
+ *   x_t = delta_t + gamma_t c_t x_{t+1},  x_T = 0;    vs_t = V_t + x_t,  vs_T = V_T
+ *   adv_t = rho^pg_t (r_t + gamma_t vs_{t+1} - V_t)
+ *   L = scale sum_{t,b} [ -adv_t log pi_t[a_t] + baseline_cost (vs_t - V_t)^2 / 2 - entropy_cost H_t ]
+ * with vs, adv and the ratios constants of the differentiation, so
+ *   dlogits[t][b][k] = scale (-adv_t (1[k == a_t] - p_k) + entropy_cost p_k (log pi_k + H_t))
+ *   dvalues[t][b][value_col] = -scale baseline_cost (vs_t - V_t),  0 in the other columns.
+ * The recursion runs in double.  vs and pg_adv (T, B) receive vs_t and adv_t
+ * when set; loss (B, 3) receives the raw per-row parts [sum_t -adv log pi[a],
+ * sum_t (vs - V)^2 / 2, sum_t H] (accumulated in double, reduced in a fixed
+ * order: no atomics), of which the caller forms scale (l0 + baseline_cost l1
+ * - entropy_cost l2).  An action outside [0, A) reads nothing outside its row
+ * and makes that row's outputs NaN.  A done inside the unroll cuts the return
+ * only; aaa_forward carries the recurrent state across it.  Every pointer is
+ * device memory; dlogits and dvalues must be 16-byte aligned. */
+typedef struct aaa_vtrace_desc {
+  int T, B, A, value_col;
+  double gamma, lambda, rho_bar, c_bar, pg_rho_bar, baseline_cost, entropy_cost, scale;
+} aaa_vtrace_desc;
+typedef struct aaa_vtrace_io {
+  const float *logits, *values;                 /* (T, B, A) */
+  const int* actions;                           /* (T, B) */
+  const float *rewards, *behaviour_logp, *done; /* (T, B); the last two may be NULL */
+  const float* bootstrap;                       /* (B) or NULL */
+  float *dlogits, *dvalues;                     /* (T, B, A), every element written */
+  float *vs, *pg_adv;                           /* (T, B) or NULL */
+  float* loss;                                  /* (B, 3) or NULL */
+} aaa_vtrace_io;
+int aaa_vtrace(const aaa_vtrace_desc* d, const aaa_vtrace_io* io, hipStream_t stream);
+
 /* ---- actor: action sampling ----
  * Policy.forward's draw (reference main_mp.py:54-58: F.softmax over the
  * logits, Categorical(probs).sample(), .log_prob(action)) for B rows of

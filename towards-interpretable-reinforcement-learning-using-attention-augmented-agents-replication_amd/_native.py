@@ -35,6 +35,7 @@ EXPORTS = (
     # added after ABI 11 without a bump (purely additive; include/aaa.h): probed by name
     "aaa_actor_core_workspace_bytes", "aaa_actor_step_core",
     "aaa_vision_enc_workspace_bytes", "aaa_vision_enc_fwd", "aaa_vision_enc_bwd",
+    "aaa_vtrace",
 )
 # include/aaa.h enum aaa_timer
 TIMER_FWD_STEP, TIMER_BPTT_STEP, TIMER_CORE_WGRAD, TIMER_ATTN_FWD, TIMER_ATTN_BWD = 0, 1, 2, 3, 4
@@ -82,6 +83,22 @@ class ActorIO(ctypes.Structure):
 class ActorCoreIO(ctypes.Structure):
     """include/aaa.h aaa_actor_core_io (aaa_actor_step_core)."""
     _fields_ = [(n, ctypes.c_void_p) for n in ("core_h", "core_c", "core_h_out", "core_c_out", "query")]
+
+
+class VtraceDesc(ctypes.Structure):
+    """include/aaa.h aaa_vtrace_desc."""
+    _fields_ = [(n, ctypes.c_int) for n in ("T", "B", "A", "value_col")] + [
+        (n, ctypes.c_double) for n in ("gamma", "lam", "rho_bar", "c_bar", "pg_rho_bar", "baseline_cost",
+                                       "entropy_cost", "scale")]
+
+
+VTRACE_IO_FIELDS = ("logits", "values", "actions", "rewards", "behaviour_logp", "done", "bootstrap",
+                    "dlogits", "dvalues", "vs", "pg_adv", "loss")
+
+
+class VtraceIO(ctypes.Structure):
+    """include/aaa.h aaa_vtrace_io."""
+    _fields_ = [(n, ctypes.c_void_p) for n in VTRACE_IO_FIELDS]
 
 
 class AdamHP(ctypes.Structure):
@@ -159,6 +176,7 @@ def load(path: str = LIB_PATH):
             "aaa_workspace_region": (I, [ctypes.POINTER(Cfg), I, ctypes.POINTER(ctypes.c_size_t),
                                          ctypes.POINTER(ctypes.c_size_t)]),
             "aaa_reinforce": (I, [I, I, I, P, P, P, ctypes.c_double, P, P, P, P]),
+            "aaa_vtrace": (I, [ctypes.POINTER(VtraceDesc), ctypes.POINTER(VtraceIO), P]),
             "aaa_sample_actions": (I, [I, I, P, ctypes.c_ulonglong, P, P, P, P, P]),
             "aaa_convlstm_packed_bytes": (S, [ctypes.POINTER(CellDesc)]),
             "aaa_convlstm_workspace_bytes": (S, [ctypes.POINTER(CellDesc)]),

@@ -17,6 +17,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "optim.h"
 #include "sampling.h"
 
 namespace aaa {
@@ -113,6 +114,130 @@ hipError_t reinforce_launch(int T, int B, int A, const float* logits, const int*
                             double gamma, float* loss, float* rn, float* dlogits, hipStream_t st) {
   hipLaunchKernelGGL(k_reinforce, dim3(B), dim3(kRfThreads), 0, st, T, B, A, logits, actions, rewards, gamma, loss,
                      rn, dlogits);
+  return hipGetLastError();
+}
+
+}  // namespace aaa
+
+namespace aaa {
+
+// --------------------------------------------------- V-trace actor-critic ---
+// The IMPALA loss of B unrolls of T steps and its cotangents (include/aaa.h
+// aaa_vtrace has the definitions).  The learner's T is 20-50, so the shape is
+// not k_reinforce's (one workgroup per row, threads chunking T): one wavefront
+// owns a row, its lanes are time steps, kVtRows rows share a workgroup.  Each
+// lane does its own step's A-wide softmax (fp32, max-subtracted) and the
+// per-step scalars in double; the recursion x_t = delta_t + g_t x_{t+1},
+// g_t = gamma_t c_t, is a backward scan of the affine maps x -> delta_t + g_t x
+// over the wave (shuffles, double).  T > 64 runs in chunks of 64 steps from
+// the last to the first, carrying x, vs and V of the chunk to the right.  A
+// done step has g_t = 0 exactly, which wipes everything to its right out of
+// the composed maps bit for bit.  The loss parts are per-lane double sums
+// reduced over the wave in a fixed order.
+constexpr int kVtRows = 4;   // wavefronts (rows) per workgroup
+
+struct VtraceArgs {
+  aaa_vtrace_desc d;
+  aaa_vtrace_io io;
+};
+
+__global__ void __launch_bounds__(kVtRows * 64) k_vtrace(const VtraceArgs P) {
+  const int T = P.d.T, B = P.d.B, A = P.d.A, vc = P.d.value_col;
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * kVtRows + (threadIdx.x >> 6);
+  if (b >= B) return;   // whole wave; no workgroup barrier below
+  const float* __restrict__ logits = P.io.logits;
+  const float* __restrict__ values = P.io.values;
+  const int* __restrict__ actions = P.io.actions;
+  const float nanf_ = __uint_as_float(0x7fc00000u);
+  // an action outside [0, A) anywhere in the row: nothing is read through it, the row's outputs are NaN
+  int bad = 0;
+  for (int t = lane; t < T; t += 64) bad |= (unsigned)actions[(size_t)t * B + b] >= (unsigned)A;
+  bad = __any(bad);
+  const double gamma = P.d.gamma, lambda = P.d.lambda, rho_bar = P.d.rho_bar, c_bar = P.d.c_bar,
+               pg_rho_bar = P.d.pg_rho_bar;
+  const float scale = (float)P.d.scale, ec = (float)P.d.entropy_cost;
+  const double vcoef = -P.d.scale * P.d.baseline_cost;
+  const double boot = P.io.bootstrap ? (double)P.io.bootstrap[b] : 0.0;
+  double x_in = 0.0, vs_in = boot, V_in = boot;   // x, vs and V of the first step to the right of the chunk
+  double l0 = 0.0, l1 = 0.0, l2 = 0.0;
+  for (int c = (T - 1) / 64; c >= 0; --c) {
+    const int t = c * 64 + lane;
+    const bool on = t < T;
+    const size_t tb = (size_t)(on ? t : T - 1) * B + b;   // idle lanes redo the last step, write nothing
+    const float* l = logits + tb * A;
+    // softmax pieces: z = sum e^{l - mx}, s = sum e^{l - mx} (l - mx)  ->  H = log z - s / z
+    float mx = -INFINITY;
+    for (int k = 0; k < A; ++k) mx = fmaxf(mx, l[k]);
+    float z = 0.f, s = 0.f;
+    for (int k = 0; k < A; ++k) {
+      const float d = l[k] - mx, e = expf(d);
+      z += e;
+      s += e * d;
+    }
+    const float logz = logf(z), H = logz - s / z;
+    const int a_raw = actions[tb];
+    const int a = (unsigned)a_raw < (unsigned)A ? a_raw : 0;
+    const float lpa = (l[a] - mx) - logz;
+    const double V = (double)values[tb * A + vc];
+    const double r = (double)P.io.rewards[tb];
+    const bool dn = P.io.done ? P.io.done[tb] != 0.f : false;
+    const double g_t = dn ? 0.0 : gamma;
+    const double ratio = P.io.behaviour_logp ? exp((double)lpa - (double)P.io.behaviour_logp[tb]) : 1.0;   // NULL: on-policy
+    const double rho = fmin(rho_bar, ratio), ct = lambda * fmin(c_bar, ratio), rho_pg = fmin(pg_rho_bar, ratio);
+    // V_{t+1}: the next lane's, or the carried one at the chunk's (or the unroll's) last step
+    double Vn = __shfl_down(V, 1, 64);
+    const bool edge = lane == 63 || t == T - 1;
+    if (edge) Vn = V_in;
+    const double delta = rho * (dn ? r - V : r + g_t * Vn - V);
+    // backward inclusive scan of x -> mb + ma x over the lanes; idle lanes are the identity
+    double ma = on ? g_t * ct : 1.0, mb = on ? delta : 0.0;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const double ra = __shfl_down(ma, o, 64), rb = __shfl_down(mb, o, 64);
+      if (lane + o < 64) {
+        mb = mb + ma * rb;
+        ma = ma * ra;
+      }
+    }
+    const double x = mb + ma * x_in;
+    const double vs = V + x;
+    double vsn = __shfl_down(vs, 1, 64);
+    if (edge) vsn = vs_in;
+    const double adv = rho_pg * (dn ? r - V : r + g_t * vsn - V);
+    x_in = __shfl(x, 0, 64);
+    vs_in = __shfl(vs, 0, 64);
+    V_in = __shfl(V, 0, 64);
+    if (!on) continue;
+    l0 += -adv * (double)lpa;
+    l1 += 0.5 * x * x;
+    l2 += (double)H;
+    const float advf = (float)adv, iz = 1.f / z;
+    float* dl = P.io.dlogits + tb * A;
+    float* dv = P.io.dvalues + tb * A;
+    for (int k = 0; k < A; ++k) {
+      const float d = l[k] - mx, p = expf(d) * iz, lp = d - logz;
+      const float g = scale * (-advf * ((k == a ? 1.f : 0.f) - p) + ec * p * (lp + H));
+      dl[k] = bad ? nanf_ : g;
+      dv[k] = bad ? nanf_ : (k == vc ? (float)(vcoef * x) : 0.f);
+    }
+    if (P.io.vs) P.io.vs[tb] = bad ? nanf_ : (float)vs;
+    if (P.io.pg_adv) P.io.pg_adv[tb] = bad ? nanf_ : advf;
+  }
+  if (P.io.loss) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      l0 += __shfl_xor(l0, o, 64);
+      l1 += __shfl_xor(l1, o, 64);
+      l2 += __shfl_xor(l2, o, 64);
+    }
+    if (lane < 3) P.io.loss[(size_t)b * 3 + lane] = bad ? nanf_ : (float)(lane == 0 ? l0 : lane == 1 ? l1 : l2);
+  }
+}
+
+hipError_t vtrace_launch(const aaa_vtrace_desc& d, const aaa_vtrace_io& io, hipStream_t st) {
+  VtraceArgs P{d, io};
+  hipLaunchKernelGGL(k_vtrace, dim3((d.B + kVtRows - 1) / kVtRows), dim3(kVtRows * 64), 0, st, P);
   return hipGetLastError();
 }
 

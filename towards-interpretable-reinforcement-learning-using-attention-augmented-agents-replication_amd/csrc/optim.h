@@ -1,4 +1,5 @@
 #pragma once
+#include "aaa.h"
 #include "common.h"
 
 namespace aaa {
@@ -34,6 +35,8 @@ hipError_t pair_flag_launch(const int* report, int* base, float* dst, hipStream_
 // loss.hip: REINFORCE (finish_episode) loss + logits cotangent, one workgroup per episode
 hipError_t reinforce_launch(int T, int B, int A, const float* logits, const int* actions, const float* rewards,
                             double gamma, float* loss, float* rn, float* dlogits, hipStream_t st);
+// loss.hip: V-trace actor-critic loss + logits / values cotangents, one wavefront per row (arguments checked by the caller)
+hipError_t vtrace_launch(const aaa_vtrace_desc& d, const aaa_vtrace_io& io, hipStream_t st);
 hipError_t sample_launch(int B, int A, const float* logits, uint64_t seed, unsigned long long* counter, int* actions,
                          float* logp, float* jac, hipStream_t st);
 

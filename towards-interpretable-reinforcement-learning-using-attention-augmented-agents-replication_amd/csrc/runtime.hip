@@ -414,6 +414,30 @@ int aaa_reinforce(int T, int B, int A, const float* logits, const int* actions, 
   return AAA_OK;
 }
 
+int aaa_vtrace(const aaa_vtrace_desc* d, const aaa_vtrace_io* io, hipStream_t stream) {
+  if (!d || !io) return fail(AAA_E_ARG, "vtrace: NULL desc or io");
+  if (d->T < 1 || d->B < 1 || d->A < 2)
+    return fail(AAA_E_ARG, "vtrace: need T, B >= 1 and A >= 2 (T=%d B=%d A=%d)", d->T, d->B, d->A);
+  if (d->value_col < 0 || d->value_col >= d->A)
+    return fail(AAA_E_ARG, "vtrace: value_col %d outside [0, %d)", d->value_col, d->A);
+  if (!(d->gamma >= 0.0 && d->gamma <= 1.0) || !(d->lambda >= 0.0 && d->lambda <= 1.0))
+    return fail(AAA_E_ARG, "vtrace: gamma and lambda must be in [0, 1]");
+  auto pos = [](double v) { return v > 0.0 && std::isfinite(v); };
+  auto nonneg = [](double v) { return v >= 0.0 && std::isfinite(v); };
+  if (!pos(d->rho_bar) || !pos(d->c_bar) || !pos(d->pg_rho_bar))
+    return fail(AAA_E_ARG, "vtrace: rho_bar, c_bar and pg_rho_bar must be positive and finite");
+  if (!nonneg(d->baseline_cost) || !nonneg(d->entropy_cost) || !nonneg(d->scale))
+    return fail(AAA_E_ARG, "vtrace: baseline_cost, entropy_cost and scale must be non-negative and finite");
+  if (!io->logits || !io->values || !io->actions || !io->rewards || !io->dlogits || !io->dvalues)
+    return fail(AAA_E_ARG, "vtrace: NULL argument (logits, values, actions, rewards, dlogits and dvalues are required)");
+  if (!aligned16(io->dlogits) || !aligned16(io->dvalues))
+    return fail(AAA_E_ALIGN, "vtrace: dlogits and dvalues must be 16-byte aligned");
+  int r = check_device();
+  if (r) return r;
+  HIPCHK(vtrace_launch(*d, *io, stream));
+  return AAA_OK;
+}
+
 int aaa_sample_actions(int B, int A, const float* logits, unsigned long long seed, unsigned long long* counter,
                        int* actions, float* logp, float* dlogp_dlogits, hipStream_t stream) {
   if (B < 1 || A < 1) return fail(AAA_E_ARG, "sample_actions: need B, A >= 1 (B=%d A=%d)", B, A);

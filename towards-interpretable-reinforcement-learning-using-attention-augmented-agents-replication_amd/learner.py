@@ -4,6 +4,9 @@ step():  pack weights -> T-step forward -> backward (3 phases) with the
 gradient buckets all-reduced (RCCL) on a side stream while later work runs.
 train_step(): step() followed by the fused Adam update of the flat params
 (main_mp.py:78; csrc/optim.hip), i.e. one complete learner iteration.
+step() takes its loss cotangents from outside; step_vtrace() /
+train_step_vtrace() compute them on the device between the forward and the
+backward (V-trace actor-critic, vtrace.py) and share everything else.
 Weights live in one flat fp32 buffer in state_dict order, grads likewise, so
 a bucket is a contiguous slice and no flatten/unflatten copies are needed.
 
@@ -40,6 +43,7 @@ from .attention import SpatialBasis
 from .optim import adam_flat_
 from .parallel import allreduce_buckets, bucket_bounds
 from .runtime import UnrollRunner
+from .vtrace import vtrace_cotangents
 
 
 class Learner:
@@ -68,8 +72,9 @@ class Learner:
         self.exp_avg_sq = torch.zeros_like(self.grads)
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=self.device)   # Adam updates applied
         self.basis = SpatialBasis(r.h, r.w).S.to(self.device).contiguous()
+        self._vt = None   # step_vtrace's (dlogits, dvalues), allocated on its first call
         self.group = group
-        self.world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
+        self.world =dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
         # per-phase gradient ownership (HEAD, CORE, VISION; tools/dp_check.py checks
         # that a phase never writes a range already handed to the all-reduce)
         self.bounds = bucket_bounds(r.offsets, r.n_params)
@@ -88,13 +93,84 @@ class Learner:
         overlaps the vision backward and never runs beside a frame-resident
         launch.  ``comm_timing`` records per-bucket events; read them with
         comm_stats() after a sync."""
+        logits, values = self._forward(frames)
+        self._backward(frames, dlogits, dvalues, overlap, comm_timing)
+        return logits, values
+
+    def step_vtrace(self, frames, actions, rewards, behaviour_logp=None, done=None, bootstrap=None,
+                    overlap: bool = True, comm_timing: bool = False, **hparams):
+        """One learner iteration on the V-trace actor-critic loss (vtrace.py;
+        include/aaa.h ``aaa_vtrace``): pack -> forward -> the loss kernel, from
+        this step's own logits / values into the learner's cotangent buffers ->
+        the backward, all-reduce schedule and guard of step().  Returns
+        (logits, values, loss_parts), loss_parts (B, 3) the raw per-row sums
+        ``[-adv log pi[a], (vs - V)^2 / 2, H]``.
+
+        actions (T, B) int32, rewards / behaviour_logp / done (T, B) fp32 and
+        bootstrap (B) fp32 should already be contiguous tensors on the learner's
+        device (anything else is converted, which copies); behaviour_logp is the
+        ``logp`` the actors returned, done and bootstrap as in ``vtrace_loss``
+        (``bootstrap="last"`` included: the inputs then have T or T-1 steps'
+        worth of rows, of which the first T-1 are used).  ``hparams`` are
+        ``vtrace_loss``'s keyword scalars.
+
+        Nothing in the iteration reads the device from the host: there is no
+        ``.item()`` and, unlike ``vtrace_loss``, no validation of the action
+        range -- an action outside [0, A) makes its row's cotangents NaN (and
+        with them the gradients), it reads nothing outside the row.  Under data
+        parallelism each rank computes the loss of its own rows and the
+        gradients are SUM-all-reduced as in step(); ``scale`` is the caller's
+        normalisation (e.g. 1 / (world * B * T))."""
+        r = self.runner
+        T, B, A = r.T, r.B, r.A
+        last = isinstance(bootstrap, str)
+        if last and bootstrap != "last":
+            raise ValueError(f"bootstrap must be a (B) tensor, None or \"last\", got {bootstrap!r}")
+        n = T - 1 if last else T
+        if n < 1:
+            raise ValueError("bootstrap=\"last\" needs an unroll of at least 2 steps")
+        if self._vt is None:   # the loss cotangents: allocated once
+            self._vt = (torch.zeros(T, B, A, device=self.device), torch.zeros(T, B, A, device=self.device))
+        dl, dv = self._vt
+
+        def dev(x, dtype, sizes):
+            if x is None:
+                return None
+            x = torch.as_tensor(x).to(device=self.device, dtype=dtype).contiguous()
+            if x.numel() not in sizes:
+                raise ValueError(f"step_vtrace: expected {' or '.join(map(str, sizes))} elements, got {tuple(x.shape)}")
+            return x
+
+        tb = (n * B, T * B)   # the kernel reads the first n steps: a contiguous prefix
+        actions, rewards = dev(actions, torch.int32, tb), dev(rewards, torch.float32, tb)
+        behaviour_logp, done = dev(behaviour_logp, torch.float32, tb), dev(done, torch.float32, tb)
+        logits, values = self._forward(frames)
+        if last:
+            bootstrap = values[T - 1, :, int(hparams.get("value_col", 0))].contiguous()
+            dl[n:].zero_()
+            dv[n:].zero_()
+        else:
+            bootstrap = dev(bootstrap, torch.float32, (B,))
+        parts = torch.empty(B, 3, device=self.device)
+        vtrace_cotangents(logits, values, actions, rewards, behaviour_logp, done, bootstrap, dl, dv, loss=parts,
+                          steps=n, **hparams)
+        self._backward(frames, dl, dv, overlap, comm_timing)
+        return logits, values, parts
+
+    def _forward(self, frames):
         r = self.runner
         r.pack(self.flat, self.packed)
         logits, values, _, _, _ = r.forward(self.flat, self.packed, self.basis, frames, self.ws, want_attn=False)
+        return logits, values
+
+    def _backward(self, frames, dlogits, dvalues, overlap, comm_timing):
+        """The backward half of an iteration: the three phases into ``grads``,
+        the all-reduce schedule and the stranded-launch guard."""
+        r = self.runner
         if self.world == 1:
             r.backward(self.flat, self.packed, self.basis, frames, self.ws, dlogits, dvalues, grads=self.grads)
             N.pair_flag(self.guard, base=self._pair_base)
-            return logits, values
+            return
         main = torch.cuda.current_stream(self.device)
         self._events = [] if comm_timing else None
         issue = dict(self.schedule[bool(overlap)])
@@ -109,7 +185,6 @@ class Learner:
             self._compute_done = torch.cuda.Event(enable_timing=True)
             self._compute_done.record(main)
         main.wait_stream(self.comm)
-        return logits, values
 
     def _allreduce(self, main, bounds, timing):
         ready = torch.cuda.Event(enable_timing=timing)
@@ -171,5 +246,13 @@ class Learner:
 
     def train_step(self, frames, dlogits, dvalues, overlap: bool = True):
         out = self.step(frames, dlogits, dvalues, overlap=overlap)
+        self.optimizer_step()
+        return out
+
+    def train_step_vtrace(self, frames, actions, rewards, behaviour_logp=None, done=None, bootstrap=None,
+                          overlap: bool = True, **hparams):
+        """step_vtrace() followed by the fused Adam update: a complete learner
+        iteration, stream-ordered, with no host round trip."""
+        out = self.step_vtrace(frames, actions, rewards, behaviour_logp, done, bootstrap, overlap=overlap, **hparams)
         self.optimizer_step()
         return out
