@@ -200,6 +200,39 @@ int aaa_core_import(const aaa_cfg* cfg, void* workspace, int t0, int n, const vo
  * are overwritten (not accumulated) by the phases that own them. */
 int aaa_backward(const aaa_cfg* cfg, const aaa_io* io, int phases, hipStream_t stream);
 
+/* Episode starts inside an unroll (additive, no ABI bump: probe by name).
+ * ``reset`` is a (T, B) fp32 mask in device memory, 16-byte aligned;
+ * reset[t][b] != 0 means row b enters step t from the reset() state
+ * (attention.py:142-149; the reference calls agent.reset() at every episode
+ * start, main_mp.py:100): ConvLSTM (h, c) = 0, and with
+ * AAA_FLAG_STATEFUL_CORE also the core's (h, c) = 0, so that step's query is
+ * QueryNetwork(0).  reset[0][b] != 0 overrides h0 / c0 / core_h0 / core_c0 of
+ * that row.  hT / cT and the saved h_t keep the true h_t: the readout of step
+ * t-1 is unaffected by a reset at t.
+ * A reset is a select, not a multiplication: nothing before it reaches
+ * anything after it, NaN and inf included (aaa_vtrace makes the same promise
+ * for ``done``).  The backward is the exact gradient of that forward: at a
+ * reset step the carried c contributes nothing, no dh / dc / dcore flows from
+ * step t to step t-1 of that row, dx of the reset step is still produced, the
+ * row's weight-gradient term dZ_t (x) h_{t-1} is zero, and dh0 / dc0 /
+ * dcore_h0 / dcore_c0 of a row with reset[0] are exactly 0.
+ * The caller passes the SAME mask to both calls; the library keeps no state,
+ * and the workspace layout and aaa_workspace_bytes do not change.
+ * reset == NULL is exactly aaa_forward_phases / aaa_backward.
+ * After the forward, AAA_WS_CORE_XH slot t holds zeros in the h half of the
+ * rows with reset[t]: the operand the kernels really used.
+ * Refused before the device is touched: AAA_E_ARG for a bf16 cfg with a mask
+ * (its readout reads h_t from the [x | h] operand slots, which a reset
+ * zeroes: cut bf16 unrolls at episode ends) and for a forward phase mask
+ * without AAA_FWD_CORE together with a mask; AAA_E_ALIGN for a mask that is
+ * not 16-byte aligned.
+ * With a mask the production fp32 frame-group kernels run their mask
+ * variants (forward: G = 8 pre-split and G = 4; BPTT: G = 8 with dx fused);
+ * every other fp32 dispatch takes the per-step kernels.  The timer variants
+ * of AAA_TIMER_FWD_STEP / AAA_TIMER_BPTT_STEP then end in ", resets". */
+int aaa_forward_resets(const aaa_cfg* cfg, const aaa_io* io, int phases, const float* reset, hipStream_t stream);
+int aaa_backward_resets(const aaa_cfg* cfg, const aaa_io* io, int phases, const float* reset, hipStream_t stream);
+
 /* Health of the multi-workgroup frame-resident ConvLSTM kernels (two or more
  * cooperating workgroups per frame: the paired and band-mode bf16 kernels and
  * the fp32 frame-group kernels, launched as ordinary grids that fit one
@@ -252,7 +285,10 @@ int aaa_pair_flag_at(float* dst, int* base, hipStream_t stream);
  * read-only, M = B*h*w pixel rows per step, pixel-major, channel fastest:
  *   AAA_WS_CORE_XH        (T+1, M, 192) fp32: slot t = [x_t | h_{t-1}], the
  *                         recurrence's and the weight gradient's operand
- *                         (slot T holds h_{T-1} only);
+ *                         (slot T holds h_{T-1} only; after
+ *                         aaa_forward_resets the h half of slot t holds
+ *                         zeros in the rows with reset[t], the operand the
+ *                         kernels really used);
  *   AAA_WS_CORE_DO        (T, M, 128) fp32: the readout's cotangent of h_t,
  *                         valid after AAA_BWD_HEAD;
  *   AAA_WS_CORE_DX        (T, M, 64) fp32: the cotangent of conv2's output
@@ -379,8 +415,10 @@ int aaa_reinforce(int T, int B, int A, const float* logits, const int* actions, 
  * order: no atomics), of which the caller forms scale (l0 + baseline_cost l1
  * - entropy_cost l2).  An action outside [0, A) reads nothing outside its row
  * and makes that row's outputs NaN.  A done inside the unroll cuts the return
- * only; aaa_forward carries the recurrent state across it.  Every pointer is
- * device memory; dlogits and dvalues must be 16-byte aligned. */
+ * only; aaa_forward carries the recurrent state across it, and
+ * aaa_forward_resets / aaa_backward_resets (fp32) cut the state with the mask
+ * reset[t] = done[t-1].  Every pointer is device memory; dlogits and dvalues
+ * must be 16-byte aligned. */
 typedef struct aaa_vtrace_desc {
   int T, B, A, value_col;
   double gamma, lambda, rho_bar, c_bar, pg_rho_bar, baseline_cost, entropy_cost, scale;

@@ -36,6 +36,7 @@ EXPORTS = (
     "aaa_actor_core_workspace_bytes", "aaa_actor_step_core",
     "aaa_vision_enc_workspace_bytes", "aaa_vision_enc_fwd", "aaa_vision_enc_bwd",
     "aaa_vtrace",
+    "aaa_forward_resets", "aaa_backward_resets",
 )
 # include/aaa.h enum aaa_timer
 TIMER_FWD_STEP, TIMER_BPTT_STEP, TIMER_CORE_WGRAD, TIMER_ATTN_FWD, TIMER_ATTN_BWD = 0, 1, 2, 3, 4
@@ -158,6 +159,8 @@ def load(path: str = LIB_PATH):
             "aaa_forward": (I, [CP, ctypes.POINTER(IO), P]),
             "aaa_backward": (I, [CP, ctypes.POINTER(IO), I, P]),
             "aaa_forward_phases": (I, [CP, ctypes.POINTER(IO), I, P]),
+            "aaa_forward_resets": (I, [CP, ctypes.POINTER(IO), I, P, P]),
+            "aaa_backward_resets": (I, [CP, ctypes.POINTER(IO), I, P, P]),
             "aaa_core_export": (I, [CP, P, I, I, P, P, P, P]),
             "aaa_core_import": (I, [CP, P, I, I, P, P, P, P]),
             "aaa_conv2d_nhwc": (I, [ctypes.POINTER(ConvDesc), P, P, P, P, P]),

@@ -35,7 +35,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .runtime import UnrollRunner
+from .runtime import UnrollRunner, _mask
 
 __all__ = ["ConvLSTMCell", "VisionNetwork", "QueryNetwork", "SpatialBasis", "spatial_softmax",
            "apply_alpha", "Agent"]
@@ -320,10 +320,11 @@ class _UnrollFn(torch.autograd.Function):
     """One library forward over T steps; its backward is the hand-written BPTT."""
 
     @staticmethod
-    def forward(ctx, runner, flat, packed, S, X, pr, pa, h0, c0, ch0, cc0, *params):
+    def forward(ctx, runner, flat, packed, S, X, pr, pa, reset, h0, c0, ch0, cc0, *params):
         ws = runner.new_workspace()
         out = runner.forward(flat, packed, S, X, ws, pr, pa, h0, c0, want_attn=True, want_state=True,
-                             core=(ch0, cc0) if runner.stateful_core else None)
+                             core=(ch0, cc0) if runner.stateful_core else None, reset=reset)
+        ctx.reset = reset   # the episode-start mask (or None): the backward cuts where the forward did
         if getattr(runner, "relu_trace", None) is not None:   # inspection hook (Agent.relu_trace)
             runner.relu_trace.append(runner.relu_masks(ws))
         logits, values, attn, hT, cT = out[:5]
@@ -341,19 +342,19 @@ class _UnrollFn(torch.autograd.Function):
             raise RuntimeError("aaa: the frames of this unroll were modified by an inplace operation after the "
                                "forward; the backward reads them again (conv1's weight gradient), as autograd "
                                "would need them unchanged")
-        want_state = bool(ctx.needs_input_grad[7] or ctx.needs_input_grad[8])
+        want_state = bool(ctx.needs_input_grad[8] or ctx.needs_input_grad[9])
         if r.stateful_core:
-            want_core = bool(ctx.needs_input_grad[9] or ctx.needs_input_grad[10])
+            want_core = bool(ctx.needs_input_grad[10] or ctx.needs_input_grad[11])
             grads, dh0, dc0, dch0, dcc0 = r.backward(ctx.flat, ctx.packed, ctx.S, ctx.X, ctx.ws, dl, dv, dhT, dcT,
                                                      want_state_grads=want_state, dcore=(dchT, dccT),
-                                                     want_core_grads=want_core)
+                                                     want_core_grads=want_core, reset=ctx.reset)
         else:
             grads, dh0, dc0 = r.backward(ctx.flat, ctx.packed, ctx.S, ctx.X, ctx.ws, dl, dv, dhT, dcT,
-                                         want_state_grads=want_state)
+                                         want_state_grads=want_state, reset=ctx.reset)
             dch0 = dcc0 = None
         ctx.ws = None
         views = [g.view(s) for g, s in zip(grads.split(r.sizes), ctx.shapes)]
-        return (None, None, None, None, None, None, None, dh0, dc0, dch0, dcc0, *views)
+        return (None, None, None, None, None, None, None, None, dh0, dc0, dch0, dcc0, *views)
 
 
 class Agent(nn.Module):
@@ -439,13 +440,17 @@ class Agent(nn.Module):
         return action, logp
 
     # -- added API ----------------------------------------------------------
-    def unroll(self, X, prev_reward=None, prev_action=None):
+    def unroll(self, X, prev_reward=None, prev_action=None, reset=None):
         """T steps in one call: X (T, B, H, W, 3) -> logits, values (T, B, A), attn (T, B, h, w, nq).
 
         Continues from the current ConvLSTM state (zero after ``reset()``) and
         leaves the final state in ``vision.vision_lstm.prev_hidden``.
+        ``reset`` (T, B) device tensor: rows with ``reset[t, b] != 0`` enter
+        step t from the ``reset()`` state, as if ``agent.reset()`` had been
+        called for that row alone (fp32 agents; ``vtrace.episode_starts``
+        makes the mask from ``done``).  The backward cuts at the same places.
         """
-        logits, values, attn = self._step(X, prev_reward, prev_action)
+        logits, values, attn = self._step(X, prev_reward, prev_action, reset)
         self.last_attention = attn
         return logits, values, attn
 
@@ -541,7 +546,7 @@ class Agent(nn.Module):
             return logits, values, attn, action, logp
         return logits, values, attn
 
-    def _step(self, X, pr, pa):
+    def _step(self, X, pr, pa, reset=None):
         if not X.is_cuda:
             raise RuntimeError("aaa: Agent runs only on the MI355X HIP path; move the agent and its "
                                "inputs to a ROCm GPU (there is no CPU fallback)")
@@ -574,7 +579,9 @@ class Agent(nn.Module):
                     raise RuntimeError(f"{name} has shape {tuple(v.shape)}, expected {(B, self.hidden_size)}")
         Xf = X.contiguous() if u8 else X.float().contiguous()
         flat, packed = self._packed_params(runner, params, self)
-        logits, values, attn, hT, cT, chT, ccT = _UnrollFn.apply(runner, flat, packed, S, Xf, pr, pa, h0, c0,
+        if reset is not None:
+            reset = _mask(reset.detach(), (T, B), X.device)
+        logits, values, attn, hT, cT, chT, ccT = _UnrollFn.apply(runner, flat, packed, S, Xf, pr, pa, reset, h0, c0,
                                                                  ch0, cc0, *params)
         cell.prev_hidden = (hT.permute(0, 3, 2, 1), cT.permute(0, 3, 2, 1))
         if stateful:

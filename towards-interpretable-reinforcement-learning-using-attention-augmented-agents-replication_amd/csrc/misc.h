@@ -114,6 +114,24 @@ hipError_t pack_lstm_all(const LstmPtrs& L, T* WpX, T* WpH, T* WdT, float* bl, T
 template <typename T>
 hipError_t gate_fwd_zx(int M, const float* cprev, float* gates, float* cnext, float* hout, T* xhnext, hipStream_t st,
                        const float* zs = nullptr, int nsl = 0, size_t sls = 0, const float* bias = nullptr);
+// Episode-start masks (resets.hip).  rs: one step's mask row [B], frame b's rows are [b*rpb, (b+1)*rpb).
+// Zero ranges of the rows of frames with rs[b] != 0: w elements at element stride es, row pitch ld.
+struct ResetZero { float* p; int ld, w, es; };
+struct ResetZeros {
+  ResetZero r[4];
+  int n = 0;
+  ResetZeros& add(float* p, int ld, int w, int es = 1) {
+    if (p) r[n++] = ResetZero{p, ld, w, es};
+    return *this;
+  }
+};
+// the zero ranges, and (dst != null) dst[row][0..cw) = rs[b] ? 0 : src[row][0..cw) for every row
+hipError_t reset_rows(const float* rs, int B, int rpb, const ResetZeros& z, const float* src, float* dst, int cw,
+                      hipStream_t st);
+// after the gate backward of step t-1: frames with rs_in[b] (reset[t]) recomputed from dh = dO and a zero dc
+// carry, d f-gate = 0 for frames with rs_c[b] (reset[t-1]); rs_in null: the last step
+hipError_t reset_gate_bwd(const float* rs_in, const float* rs_c, int M, int P, const float* dO, const float* gates,
+                          const float* cprev, const float* ccur, float* dC, float* dz, hipStream_t st);
 hipError_t pack_f32(const F32Pack& p, hipStream_t st);
 // Channel-chunk-major copy of conv-GEMM rows (ConvGeo::cmaj): row r's K = taps x Cin
 // (tap-major) -> dst[r][(c / BK) * taps * BK + tap * BK + c % BK]

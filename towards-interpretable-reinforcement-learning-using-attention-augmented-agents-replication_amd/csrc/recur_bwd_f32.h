@@ -213,6 +213,11 @@ struct RecBwdF32Params {
   const u32x4* Wx6p = nullptr;  // DX: the dx rows, paired the same way
   float* dx = nullptr;          // DX: (T, B, P, 64) <- conv2's output gradient (dY2)
   float* dxb = nullptr;         // DX: (B, 64) <- its pixel-and-step sums (conv2's bias gradient per frame)
+  // RST kernel: the episode-start mask (T, B) of the forward (recur_f32.h RST), frame-uniform here too.
+  // After the exchange sums of step s, reset[s][b] selects 0 for the recurrent dh_{s-1} and for the dc
+  // carry handed to step s-1 (what T-1 always was: nothing flows in), and the gate backward of step s-1
+  // reads c_{s-2} as 0 when reset[s-1][b].  dx and the bias partials are unchanged; so are the waits.
+  const float* reset = nullptr;
 };
 
 #ifdef AAA_STAMPS
@@ -236,7 +241,7 @@ __device__ uint64_t aaa_b32_stamps[512 * 64 * 4];
 // borderless, the zero pixel kPsZP (the image's last), pixel pitch 400 B, chunk (part * 4 + g) * 2 + hh for the
 // 16-row group g) -- the gate backward splits each dZ value once as it writes the image,
 // and the K loop reads bf16 parts only (no per-wave split of the B fragments).
-template <int ABL = 0, bool S6 = false, int PDS = kB32PD, bool PS = false, bool DX = false>
+template <int ABL = 0, bool S6 = false, int PDS = kB32PD, bool PS = false, bool DX = false, bool RST = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 k_convlstm_bwd_f32(RecBwdF32Params p) {
   static_assert(!PS || S6, "PS: the split-product kernel");
@@ -689,6 +694,18 @@ k_convlstm_bwd_f32(RecBwdF32Params p) {
         dxs += v;
       }
     }
+    bool rcp = false;   // RST: step s-1 entered from reset(), its c_{s-2} is 0
+    if constexpr (RST) {
+      if (p.reset[(size_t)s * p.B + b] != 0.f) {   // step s entered from reset(): nothing flows to step s-1
+#pragma unroll
+        for (int n = 0; n < NG; ++n) {
+          dhv[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) dcr[n][e] = 0.f;
+        }
+      }
+      rcp = s >= 1 && p.reset[(size_t)(s - 1) * p.B + b] != 0.f;
+    }
     if (s == 0) {   // dh0 = dh_{-1}: no gate backward
       if (p.dh0) {
 #pragma unroll
@@ -714,8 +731,8 @@ k_convlstm_bwd_f32(RecBwdF32Params p) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float di, df, dcg, dout;
-        gate_bwd(dhv[n][e] + gpre[n][0][e], gpre[n][1 + e], gpre[n][5][e], gpre[n][6][e], dcr[n][e], di, df, dcg,
-                 dout);
+        gate_bwd(dhv[n][e] + gpre[n][0][e], gpre[n][1 + e], rcp ? 0.f : gpre[n][5][e], gpre[n][6][e], dcr[n][e], di,
+                 df, dcg, dout);
         const f32x4 z{di, df, dcg, dout};
         bs[e] += z;
         zg[e] = z;
@@ -771,8 +788,12 @@ inline hipError_t convlstm_bwd_f32(RecBwdF32Params& p, hipStream_t st, bool s6 =
     return launch_resident(reinterpret_cast<const void*>(&k_convlstm_bwd_f32<0, true, 4>), f32_grid(p.B, 8), 256, p,
                            st);
 #endif
+  if (p.reset && !(s6 && p.dx)) return hipErrorInvalidValue;   // the mask variant: the production kernel's
   if (s6 && p.dx) {   // the production kernel: dx fused (DX)
     if (!p.Wb6p || !p.Wx6p || !p.dxb) return hipErrorInvalidValue;
+    if (p.reset)
+      return launch_resident(reinterpret_cast<const void*>(&k_convlstm_bwd_f32<0, true, 4, true, true, true>),
+                             f32_grid(p.B, 8), 256, p, st);
     return launch_resident(reinterpret_cast<const void*>(&k_convlstm_bwd_f32<0, true, 4, true, true>),
                            f32_grid(p.B, 8), 256, p, st);
   }

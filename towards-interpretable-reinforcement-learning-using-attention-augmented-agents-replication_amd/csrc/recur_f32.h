@@ -127,6 +127,12 @@ struct RecF32Params {
   short colhb[128];    // column -> top-left image pixel of its 3x3 window (padding columns: pixel P-1's)
   const u32x2* Wf6 = nullptr;   // S6: the three-way split of Wf (k_split_frag)
   const u32x4* Wf6p = nullptr;  // the pre-split kernel's stream: quads 2j, 2j+1 of a part side by side per lane
+  // RST kernels: the episode-start mask (T, B), reset[t][b] != 0: frame b enters step t from reset().
+  // Frame-uniform, so the two run-time cases are the ones t = 0 already has: the h-part skipped (and the
+  // A stream restarted) and c_{t-1} read as 0.  The epilogue of step t-1 then writes zeros for h_{t-1}
+  // into XH slot t and its own channels of the h image (the partners' and the weight gradient's
+  // operand; Hs keeps the true h_{t-1}).  Waits, flags and deadlines are those of the plain kernel.
+  const float* reset = nullptr;
 };
 
 // Blocks of the launch: 8 * G * ceil(B / 8) (XCD-local frame groups).
@@ -163,7 +169,7 @@ __device__ uint64_t aaa_f32_clocks[512 * 64 * 5];   // s_memtime (shader clock) 
 // B fragment is split by one wave instead of two (the split is VALU work the MFMAs
 // wait on: tools/ubench/f32rec "S6 no B split"), at twice the per-wave A stream
 // (the four waves of a workgroup then read the same A quads).  PDW: A quads in flight.
-template <int G, int ABL = 0, bool S6 = false, bool WIDE = false, int PDW = kF32PD>
+template <int G, int ABL = 0, bool S6 = false, bool WIDE = false, int PDW = kF32PD, bool RST = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 k_convlstm_fwd_f32(RecF32Params p) {
   static_assert(!WIDE || (S6 && G == 8), "WIDE: the S6 kernel at G = 8");
@@ -433,7 +439,12 @@ k_convlstm_fwd_f32(RecF32Params p) {
           });
       }
     }
-    const bool hpart = t > 0 || !p.h0_zero;
+    bool rst = false, rnx = false;   // RST: frame b enters this step / the next one from reset()
+    if constexpr (RST) {
+      rst = p.reset[(size_t)t * p.B + b] != 0.f;
+      rnx = t + 1 < p.T && p.reset[(size_t)(t + 1) * p.B + b] != 0.f;
+    }
+    const bool hpart = (t > 0 || !p.h0_zero) && !rst;
     if (exch) partner_store();
     barrier_lds();   // every wave is done with x_t; the partners' h_{t-1} is in the image
     AAA_F32_STAMP(t, 1);
@@ -501,13 +512,13 @@ k_convlstm_fwd_f32(RecF32Params p) {
           const int chl = 2 * g + hh, ch = 8 * (rbg0 + r) + chl;
           float gi, gf, gc, go, cc, h;
           GateFwd::run(acc[r][c][4 * g] + bz[r][g][0], acc[r][c][4 * g + 1] + bz[r][g][1],
-                       acc[r][c][4 * g + 2] + bz[r][g][2], acc[r][c][4 * g + 3] + bz[r][g][3], cst[r][c][g], gi, gf,
+                       acc[r][c][4 * g + 2] + bz[r][g][2], acc[r][c][4 * g + 3] + bz[r][g][3], rst ? 0.f : cst[r][c][g], gi, gf,
                        gc, go, cc, h);
           cst[r][c][g] = cc;
           *reinterpret_cast<f32x4*>(stg + r32 * kF32GP + 16 * chl) = f32x4{gi, gf, gc, go};
           *reinterpret_cast<float*>(stg + kF32SG + r32 * 48 + 4 * chl) = cc;
           *reinterpret_cast<float*>(stg + kF32SG + 32 * 48 + r32 * 48 + 4 * chl) = h;
-          if (pp >= 0) *reinterpret_cast<float*>(him + ip * 512 + sw16(ch >> 2, pp) + (ch & 3) * 4) = h;
+          if (pp >= 0) *reinterpret_cast<float*>(him + ip * 512 + sw16(ch >> 2, pp) + (ch & 3) * 4) = rnx ? 0.f : h;
         }
         __builtin_amdgcn_wave_barrier();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -619,7 +630,7 @@ __device__ __forceinline__ void ps_store_group(unsigned char* img, int pix_off, 
 // 2 (w >> 1), +1 (each A quad streamed by two waves, each B part read by two).  The A stream
 // (L2 -> L1 -> VGPR, no LDS room left beside the split images) is the kernel's bound
 // (tools/ubench/f32ps: no A loads -29 %), so MAP 1 halves its L1 traffic.
-template <int ABL = 0, int MAP = 1, int PD = 8>
+template <int ABL = 0, int MAP = 1, int PD = 8, bool RST = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 k_convlstm_fwd_f32ps(RecF32Params p) {
   static_assert(8 % PD == 0 && PD >= 4 && PD <= kF32PD, "PD");   // slot = quad % PD; a pair never wraps
@@ -841,7 +852,12 @@ k_convlstm_fwd_f32ps(RecF32Params p) {
         for (int c = 0; c < NCB; ++c) xb[c] = xn[c];
       }
     }
-    const bool hpart = t > 0 || !p.h0_zero;
+    bool rst = false, rnx = false;   // RST: frame b enters this step / the next one from reset()
+    if constexpr (RST) {
+      rst = p.reset[(size_t)t * p.B + b] != 0.f;
+      rnx = t + 1 < p.T && p.reset[(size_t)(t + 1) * p.B + b] != 0.f;
+    }
+    const bool hpart = (t > 0 || !p.h0_zero) && !rst;
     if (exch) partner_store();
     barrier_lds();   // every wave is done with x_t; the partners' h_{t-1} is in the image
     AAA_F32_STAMP(t, 1);
@@ -890,7 +906,7 @@ k_convlstm_fwd_f32ps(RecF32Params p) {
             const int chl = 2 * g + hh;
             float gi, gf, gc, go, cc, h;
             GateFwd::run(acc[r][c][4 * g] + bz[r][g][0], acc[r][c][4 * g + 1] + bz[r][g][1],
-                         acc[r][c][4 * g + 2] + bz[r][g][2], acc[r][c][4 * g + 3] + bz[r][g][3], cst[r][c][g], gi, gf,
+                         acc[r][c][4 * g + 2] + bz[r][g][2], acc[r][c][4 * g + 3] + bz[r][g][3], rst ? 0.f : cst[r][c][g], gi, gf,
                          gc, go, cc, h);
             cst[r][c][g] = cc;
             *reinterpret_cast<f32x4*>(stg + kPsGT + r32 * 144 + 16 * chl) = f32x4{gi, gf, gc, go};
@@ -929,11 +945,13 @@ k_convlstm_fwd_f32ps(RecF32Params p) {
         *reinterpret_cast<u32x4*>(hs + 4) = h1;
         const __amdgpu_buffer_rsrc_t rs = xh_rsrc(t + 1);
         const uint32_t off = (uint32_t)((px * 192 + 64 + 16 * kh + 8 * half) * 4);
-        __builtin_amdgcn_raw_buffer_store_b128(h0, rs, off, 0, kSC1);
-        __builtin_amdgcn_raw_buffer_store_b128(h1, rs, off + 16, 0, kSC1);
+        const u32x4 z4 = {0u, 0u, 0u, 0u};   // (rnx: the next step starts an episode, its h_{t-1} is 0)
+        __builtin_amdgcn_raw_buffer_store_b128(rnx ? z4 : h0, rs, off, 0, kSC1);
+        __builtin_amdgcn_raw_buffer_store_b128(rnx ? z4 : h1, rs, off + 16, 0, kSC1);
         // the split image's lane half ``half`` holds channels {4 half .. +3, 8 + 4 half .. +3}
-        const f32x4 va = *reinterpret_cast<const f32x4*>(ht + 16 * half);
-        const f32x4 vb = *reinterpret_cast<const f32x4*>(ht + 32 + 16 * half);
+        f32x4 va = *reinterpret_cast<const f32x4*>(ht + 16 * half);
+        f32x4 vb = *reinterpret_cast<const f32x4*>(ht + 32 + 16 * half);
+        if (rnx) va = vb = f32x4{0.f, 0.f, 0.f, 0.f};
         const float x8[8] = {va[0], va[1], va[2], va[3], vb[0], vb[1], vb[2], vb[3]};
         bf16x8 hi, mid, lo;
         split3_bf16(x8, hi, mid, lo);
@@ -971,6 +989,10 @@ inline bool f32_fwd_presplit(bool s6, int G, int P) {
   return s6 && G == 8 && P <= kPsZP;
 }
 
+// Whether the frame-group forward has a mask variant (RST) for this launch: the production S6 kernels
+// (G = 8 pre-split, G = 4); elsewhere a mask takes the per-step kernels.
+inline bool f32_fwd_resets(bool s6, int G, int P) { return s6 && (G == 4 || f32_fwd_presplit(s6, G, P)); }
+
 inline hipError_t convlstm_fwd_f32(RecF32Params& p, int G, hipStream_t st, bool s6 = false) {
   if (!f32_rec_fits(p.h, p.w) || p.P != p.h * p.w || p.B < 1 || p.T < 1 || !p.flags || !p.report || p.spin < 0)
     return hipErrorInvalidValue;
@@ -983,6 +1005,12 @@ inline hipError_t convlstm_fwd_f32(RecF32Params& p, int G, hipStream_t st, bool 
   // G = 8, S6, P <= 128: the pre-split images (k_convlstm_fwd_f32ps); larger grids the in-loop
   // split (AAA_F32_PRESPLIT=0 selects it everywhere in ablation builds)
   const bool ps = f32_fwd_presplit(s6, G, p.P);
+  if (p.reset) {   // the mask variants (one launch shape, the waits and flags of the plain kernels)
+    if (!f32_fwd_resets(s6, G, p.P)) return hipErrorInvalidValue;
+    const void* kr = ps ? reinterpret_cast<const void*>(&k_convlstm_fwd_f32ps<0, 1, 8, true>)
+                        : reinterpret_cast<const void*>(&k_convlstm_fwd_f32<4, 0, true, false, kF32PD, true>);
+    return launch_resident(kr, f32_grid(p.B, G), 256, p, st);
+  }
   const void* k = ps       ? reinterpret_cast<const void*>(&k_convlstm_fwd_f32ps<0, 1, 8>)
                   : G == 8 ? (s6 ? reinterpret_cast<const void*>(&k_convlstm_fwd_f32<8, 0, true, true, 4>)
                                  : reinterpret_cast<const void*>(&k_convlstm_fwd_f32<8>))

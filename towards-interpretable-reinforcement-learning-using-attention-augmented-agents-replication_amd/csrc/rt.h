@@ -528,7 +528,7 @@ static hipError_t step_gemm_splitk(const T* W, int ldw, int wrows, const T* src,
 }
 template <typename T, typename GT>
 static int fused_step(const T* WpXH, const T* xht, int h, int w, int M, const EpiConvLstmFwd<T, GT>& ep,
-                      hipStream_t st, float* zpart = nullptr) {
+                      hipStream_t st, float* zpart = nullptr, bool resets = false) {
   using EF = EpiConvLstmFwd<T, GT>;
   const ConvGeo g = ConvGeo{192, 192, 0, h, w, h, w, 3, 1, 1, 0}.prep();
   const uint32_t xh_bytes = (uint32_t)((size_t)M * 192 * sizeof(T));
@@ -540,8 +540,9 @@ static int fused_step(const T* WpXH, const T* xht, int h, int w, int M, const Ep
   // there is no split-K scratch
   const int ftile = env_int("AAA_FUSED_TILE", f32 ? (f32_split6() ? (zpart ? 18 : 13) : 4) : 9);
   TimerScope tim(AAA_TIMER_FWD_STEP, st, 2.0 * M * 512 * 1728,
-                 strf("%s fused [x|h] step, K=1728, AAA_FUSED_TILE %d%s [kernel: EpiConvLstmFwd]", f32 ? "fp32" : "bf16",
-                      ftile, f32 && ftile >= 13 && ftile <= 16 ? " (bf16x6 split products)" : ""));
+                 strf("%s fused [x|h] step, K=1728, AAA_FUSED_TILE %d%s [kernel: EpiConvLstmFwd]%s", f32 ? "fp32" : "bf16",
+                      ftile, f32 && ftile >= 13 && ftile <= 16 ? " (bf16x6 split products)" : "",
+                      resets ? ", resets" : ""));
   if (ftile == 17 || ftile == 18) {   // split-K (bf16x6 split products)
     if constexpr (!f32 || !std::is_same<GT, float>::value) {
       return fail(AAA_E_ARG, "AAA_FUSED_TILE %d: fp32 split-product tiles only", ftile);
@@ -617,7 +618,9 @@ template <typename T> int pack_impl(const Layout& L, const float* prm, char* pk,
 template <typename T, typename OT>
 int vision_fwd(const Layout& L, int F, const char* pk, const float* prm, const void* frames, T* Xp, T* Y1, OT* out,
                int out_ld, hipStream_t st, bool xp_full = true, std::string* ran = nullptr);   // ran <- the kernels taken
-template <typename T> int forward_impl(const Layout& L, const aaa_io* io, hipStream_t st, int phases);
+// reset: the episode-start mask (T, B) of aaa_forward_resets / aaa_backward_resets (fp32 only), or null
+template <typename T>
+int forward_impl(const Layout& L, const aaa_io* io, hipStream_t st, int phases, const float* reset = nullptr);
 template <typename T>
 int lstm_wgrad(const T* dz, const T* xh, int rows, int h, int w, float* gW, hipStream_t s, bool aux);
 template <typename T>
@@ -629,6 +632,7 @@ template <typename T>
 int vision_bwd_alone(const Layout& L, const char* pk, const void* frames, const T* dy2, const T* y1, T* xp, T* dy1,
                      void* part, size_t part_bytes, int F, float* gW2, float* gW1, float* gb1, hipStream_t st,
                      const void* xp_frames, bool* fused);
-template <typename T> int backward_impl(const Layout& L, const aaa_io* io, int phases, hipStream_t st);
+template <typename T>
+int backward_impl(const Layout& L, const aaa_io* io, int phases, hipStream_t st, const float* reset = nullptr);
 
 }  // namespace aaa

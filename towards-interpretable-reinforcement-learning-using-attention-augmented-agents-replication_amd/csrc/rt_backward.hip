@@ -524,7 +524,7 @@ int vision_bwd_alone(const Layout& L, const char* pk, const void* frames, const 
 // step by step from t = T-1 (the carries dh, dc of the core state flow through
 // the LSTMCell's W_hh and the query MLP into step t-1); every weight gradient
 // is then one batched GEMM over all frames from the saved per-step operands.
-static int head_backward_stateful(const Layout& L, const aaa_io* io, hipStream_t st) {
+static int head_backward_stateful(const Layout& L, const aaa_io* io, hipStream_t st, const float* reset) {
   constexpr int NTF = CF::NT;
   char* ws = (char*)io->workspace;
   const char* pk = (const char*)io->packed;
@@ -549,6 +549,10 @@ static int head_backward_stateful(const Layout& L, const aaa_io* io, hipStream_t
       EpiLstmCellBwdS ep{Wf(L.LG) + f0 * 1024, CC + f0 * 256, CC + (f0 + B) * 256, dhc, dcc, Wf(L.dLG) + f0 * 1024, B};
       HIPCHK((head_gemm<LdRowsT, LdRows>(pa, pb, ep, 256, B, L.ldy, 1, st)));
     }
+    // rows that entered step t from reset(): c_{t-1} was 0 (d f-gate stored as 0) and no dc flows to step t-1
+    if (reset)
+      HIPCHK(reset_rows(reset + f0, B, 1, ResetZeros{}.add(Wf(L.dLG) + f0 * 1024 + 1, 1024, 256, 4).add(dcc, 256, 256),
+                        nullptr, nullptr, 0, st));
     {  // [d answer | d h_{t-1} (recurrent part)] = [W_ih | W_hh]^T dgates
       LTf::Params pa{(const float*)(pk + L.k_Wihhp), 512, 512};
       LRfj::Params pb{Wf(L.dLG) + f0 * 1024, 1024, B};
@@ -592,6 +596,8 @@ static int head_backward_stateful(const Layout& L, const aaa_io* io, hipStream_t
       EpiStoreAddT ep{dhc, dAOX + f0 * 512 + 256, 256, 512, 256, B};
       HIPCHK((head_gemm<LdRowsT, LdRows>(pa, pb, ep, 256, B, 128, 1, st)));
     }
+    if (reset)   // ... and no dh: h_{t-1} was 0 for both of its readers
+      HIPCHK(reset_rows(reset + f0, B, 1, ResetZeros{}.add(dhc, 256, 256), nullptr, nullptr, 0, st));
   }
   if (io->dcore_h0) HIPCHK(hipMemcpyAsync(io->dcore_h0, dhc, sB, hipMemcpyDeviceToDevice, st));
   if (io->dcore_c0) HIPCHK(hipMemcpyAsync(io->dcore_c0, dcc, sB, hipMemcpyDeviceToDevice, st));
@@ -617,7 +623,11 @@ static int head_backward_stateful(const Layout& L, const aaa_io* io, hipStream_t
   HIPCHK(colsum(Wf(L.dQf), qd, F, qd, grads + L.poff[Q4B], st));
   if ((rc = wgrad(Wf(L.dq2s), qd, qd, Wf(L.q1s), 128, 128, grads + L.poff[Q2W], 128))) return rc;
   HIPCHK(colsum(Wf(L.dq2s), qd, F, qd, grads + L.poff[Q2B], st));
-  if ((rc = wgrad(Wf(L.dq1s), 128, 128, CH, 256, 256, grads + L.poff[Q0W], 256))) return rc;
+  // the query MLP's input: CH slots 0..T-1, or with a mask the h half of the [answer | h] rows it read (zeros
+  // in the rows of an episode start: forward_tail_stateful)
+  if ((rc = reset ? wgrad(Wf(L.dq1s), 128, 128, AOX + 256, 512, 256, grads + L.poff[Q0W], 256)
+                  : wgrad(Wf(L.dq1s), 128, 128, CH, 256, 256, grads + L.poff[Q0W], 256)))
+    return rc;
   HIPCHK(colsum(Wf(L.dq1s), 128, F, 128, grads + L.poff[Q0B], st));
   F32Unpack up;
   up.gW1p = Wf(L.gW1p); up.gWihp = Wf(L.gWihp); up.gblc = Wf(L.gblc); up.gWhd = Wf(L.gWhd); up.gbhd = Wf(L.gbhd);
@@ -631,7 +641,7 @@ static int head_backward_stateful(const Layout& L, const aaa_io* io, hipStream_t
 }
 
 template <typename T>
-int backward_impl(const Layout& L, const aaa_io* io, int phases, hipStream_t st) {
+int backward_impl(const Layout& L, const aaa_io* io, int phases, hipStream_t st, const float* reset) {
   using C = CfgFor<T>;
   // bf16 path: the fp32 tail GEMMs on the bf16 MFMA with split operands (AAA_TAIL_SPLIT3=0: fp32 MFMA)
   TailPrecision tail_prec(std::is_same<T, __bf16>::value && env_int("AAA_TAIL_SPLIT3", 1),
@@ -658,7 +668,7 @@ int backward_impl(const Layout& L, const aaa_io* io, int phases, hipStream_t st)
       HIPCHK(prologue<T>(z, 0, nullptr, (T*)nullptr, F, L.A, L.ldy, io->dlogits, io->dvalues, Wf(L.dY), st));
     }
     if (L.sc) {
-      const int rc = head_backward_stateful(L, io, st);
+      const int rc = head_backward_stateful(L, io, st, reset);
       if (rc) return rc;
     } else {
     std::unique_ptr<TimerScope> tail(new TimerScope(AAA_TIMER_TAIL_BWD, st, 2.0 * F * (tail_fwd_flop(L) + 2.0 * 256 * L.ldy),
@@ -937,8 +947,28 @@ int backward_impl(const Layout& L, const aaa_io* io, int phases, hipStream_t st)
     const bool g16 = gates_f16(L.dt, M);
     const int fb = frames_bwd(L, g16);   // the whole chain in one frame-resident launch (workgroups per frame)
     // fp32: the frame-group BPTT (recur_bwd_f32.h, G = 8) behind the forward's frame-group kernel
-    const bool fb32 = std::is_same<T, float>::value && f32_frames(L) == 8 && env_int("AAA_F32_FRAMES_BWD", 1);
+    // (a mask: the frame-group BPTT's RST variant, the production split-product kernel with dx fused; else the
+    // per-step chain)
+    const bool fb32 = std::is_same<T, float>::value && (!reset || f32_split6()) && f32_frames(L) == 8 &&
+                      env_int("AAA_F32_FRAMES_BWD", 1);
     if (fb32) part = nullptr;   // the kernel writes per-(step, frame) bias partials, step T-1's included
+    // Episode starts (reset != null, fp32): the step kernels run as they are, then resets.hip's
+    // k_reset_gate_bwd rewrites the rows of step t-1's gate backward that an episode start at t or
+    // t-1 changes (fix below).  The gate-bias gradient is then the column sum of the final dZ, not
+    // of partials taken before the rewrite.
+    if (reset) part = nullptr;
+    auto fix = [&](int t) -> int {   // after the gate backward of step t-1 (t = T: the last step's)
+      if (!reset) return AAA_OK;
+      if constexpr (std::is_same<T, float>::value) {
+        HIPCHK(reset_gate_bwd(t < L.T ? reset + (size_t)t * L.B : nullptr, reset + (size_t)(t - 1) * L.B, M, P,
+                              Wf(L.dO) + (size_t)(t - 1) * M * 128, Wf(L.Gt) + (size_t)(t - 1) * M * 512,
+                              Wf(L.Cst) + (size_t)(t - 1) * M * 128, Wf(L.Cst) + (size_t)t * M * 128, Wf(L.dC),
+                              Wf(L.dZ) + (size_t)(t - 1) * M * 512, st));
+        return AAA_OK;
+      } else {
+        return fail(AAA_E_ARG, "episode-start masks: fp32 only");
+      }
+    };
     if (fb) {
     } else if (g16)
       HIPCHK((gate_bwd_last<T, _Float16>(M, bj, Wf(L.dO) + (size_t)t1 * M * 128, io->dhT,
@@ -951,6 +981,10 @@ int backward_impl(const Layout& L, const aaa_io* io, int phases, hipStream_t st)
                                       Wf(L.Cst) + (size_t)t1 * M * 128, Wf(L.Cst) + (size_t)(t1 + 1) * M * 128,
                                       Wf(L.dC), Wt(L.dZ) + (size_t)t1 * M * 512,
                                       part ? part + (size_t)t1 * ntj * 512 : nullptr, st)));
+    if (!fb) {
+      const int rc = fix(L.T);
+      if (rc) return rc;
+    }
     misc.reset();
     const uint32_t dz_bytes = (uint32_t)((size_t)M * 512 * L.esz);  // one step slice of dZ
     const T* WdTh = (const T*)(pk + L.k_WdTl) + (size_t)64 * 4608;
@@ -1006,6 +1040,7 @@ int backward_impl(const Layout& L, const aaa_io* io, int phases, hipStream_t st)
                            Wf(L.dZp), io->dh0, Wf(L.xpart), (int*)(ws + L.rflags), rep, pair_budget(L.T),
                            L.T, L.B, L.h, L.w, L.P, {}};
         const bool s6 = f32_split6();
+        rp.reset = reset;
         rp.Wb6 = (const u32x2*)(pk + L.k_Wb6);
         if (s6) {   // dx fused (DX): conv2's output gradient and its bias partials from the same K loop
           rp.Wx6 = (const u32x2*)(pk + L.k_Wx6);
@@ -1020,7 +1055,7 @@ int backward_impl(const Layout& L, const aaa_io* io, int phases, hipStream_t st)
           const double dh_steps = L.T - 1 + ((io->dh0 || s6) ? 1 : 0);
           TimerScope tim(AAA_TIMER_BPTT_STEP, st, 2.0 * M * 4608 * (128.0 * dh_steps + (s6 ? 64.0 * L.T : 0.0)),
                          s6 ? strf("fp32 frame-group BPTT + dx (bf16x6 split products), %d steps per launch, 8 WG "
-                                   "per frame [kernel: k_convlstm_bwd_f32]", L.T)
+                                   "per frame [kernel: k_convlstm_bwd_f32]%s", L.T, reset ? ", resets" : "")
                             : strf("fp32 frame-group BPTT (dh rows), %d steps per launch, 8 WG per frame "
                                    "[kernel: k_convlstm_bwd_f32]", L.T));
           HIPCHK(convlstm_bwd_f32(rp, st, s6));
@@ -1038,7 +1073,7 @@ int backward_impl(const Layout& L, const aaa_io* io, int phases, hipStream_t st)
       if (!prev && !io->dh0) break;
       const ConvGeo g = ConvGeo{512, 512, 0, L.h, L.w, L.h, L.w, 3, 1, 1, 1}.prep();
       const T* dzt = Wt(L.dZ) + (size_t)t * M * 512;
-      TimerScope tim(AAA_TIMER_BPTT_STEP, st, 2.0 * M * 128 * 4608, strf("%s dh dgrad + fused gate bwd, K=4608, AAA_BPTT_TILE %d%s", std::is_same<T, float>::value ? "fp32" : "bf16", bwd_tile, g16 ? ", fp16 gates [kernel: EpiConvLstmBwd]" : " [kernel: EpiConvLstmBwd]"));
+      TimerScope tim(AAA_TIMER_BPTT_STEP, st, 2.0 * M * 128 * 4608, strf("%s dh dgrad + fused gate bwd, K=4608, AAA_BPTT_TILE %d%s%s", std::is_same<T, float>::value ? "fp32" : "bf16", bwd_tile, g16 ? ", fp16 gates [kernel: EpiConvLstmBwd]" : " [kernel: EpiConvLstmBwd]", reset ? ", resets" : ""));
       if constexpr (std::is_same<T, float>::value) {
         if (fixk && prev) {   // split-K, the last slice of each tile runs the gate backward (EpiSliceFix)
           if (!L.dhs) return fail(AAA_E_ARG, "AAA_BPTT_TILE %d: split-K needs B*P < 8192 (got %d)", bwd_tile, M);
@@ -1057,6 +1092,7 @@ int backward_impl(const Layout& L, const aaa_io* io, int phases, hipStream_t st)
           else
             HIPCHK((step_gemm_splitk<GemmCfgS6<32, 32, 128, 1, 1, 8>>(WdTh, 4608, 128, dzt, g, M, dz_bytes, ef, 128,
                                                                       4608, st, ns, true)));
+          if (const int rc = fix(t)) return rc;
           continue;
         }
         if ((bwd_tile == 30 || bwd_tile == 31) && prev) {   // split-K: K-slice partials, then the gate backward
@@ -1076,6 +1112,7 @@ int backward_impl(const Layout& L, const aaa_io* io, int phases, hipStream_t st)
                                           Wf(L.Cst) + (size_t)t * M * 128, Wf(L.dC), Wt(L.dZ) + (size_t)(t - 1) * M * 512,
                                           part ? part + (size_t)(t - 1) * ntj * 512 : nullptr, st, ns,
                                           (size_t)M * 128)));
+          if (const int rc = fix(t)) return rc;
           continue;
         }
       }
@@ -1192,6 +1229,8 @@ int backward_impl(const Layout& L, const aaa_io* io, int phases, hipStream_t st)
       };
       const hipError_t e = g16 ? step(_Float16{}) : step(float{});
       HIPCHK(e);
+      if (prev)
+        if (const int rc = fix(t)) return rc;
     }
     { const int rc0 = flush(0); if (rc0) return rc0; }
     misc.reset(new TimerScope(AAA_TIMER_MISC, st, 0.0, "gate-bias column sums, state grads out, grad unpack"));
@@ -1202,6 +1241,9 @@ int backward_impl(const Layout& L, const aaa_io* io, int phases, hipStream_t st)
       HIPCHK(colsum<float>(Wf(L.dZp), 512, L.T * L.B, 512, Wf(L.gbl), st));
     else if (part) HIPCHK(colsum<float>(part, 512, L.T * ntj, 512, Wf(L.gbl), st));
     else HIPCHK(colsum<T>(Wt(L.dZ), 512, F * P, 512, Wf(L.gbl), st));
+    if (reset)   // rows whose episode starts at step 0: h0 / c0 were not read, their cotangents are exactly 0
+      HIPCHK(reset_rows(reset, L.B, P, ResetZeros{}.add(Wf(L.dC), 128, 128).add(io->dh0, 128, 128), nullptr, nullptr, 0,
+                        st));
     if (io->dc0) HIPCHK(hipMemcpyAsync(io->dc0, Wf(L.dC), (size_t)M * 128 * 4, hipMemcpyDeviceToDevice, st));
     if (ax) HIPCHK(stream_order(ax, st));   // join
     LstmGrads lg;
@@ -1243,7 +1285,7 @@ template int vision_bwd_alone<float>(const Layout&, const char*, const void*, co
 template int vision_bwd_alone<__bf16>(const Layout&, const char*, const void*, const __bf16*, const __bf16*, __bf16*,
                                       __bf16*, void*, size_t, int, float*, float*, float*, hipStream_t, const void*,
                                       bool*);
-template int backward_impl<float>(const Layout&, const aaa_io*, int, hipStream_t);
-template int backward_impl<__bf16>(const Layout&, const aaa_io*, int, hipStream_t);
+template int backward_impl<float>(const Layout&, const aaa_io*, int, hipStream_t, const float*);
+template int backward_impl<__bf16>(const Layout&, const aaa_io*, int, hipStream_t, const float*);
 
 }  // namespace aaa

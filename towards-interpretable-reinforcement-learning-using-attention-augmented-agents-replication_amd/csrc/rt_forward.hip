@@ -168,10 +168,10 @@ int vision_fwd(const Layout& L, int F, const char* pk, const float* prm, const v
 }
 
 template <typename T>
-static int forward_tail(const Layout& L, const aaa_io* io, hipStream_t st);
+static int forward_tail(const Layout& L, const aaa_io* io, hipStream_t st, const float* reset = nullptr);
 
 template <typename T>
-int forward_impl(const Layout& L, const aaa_io* io, hipStream_t st, int phases) {
+int forward_impl(const Layout& L, const aaa_io* io, hipStream_t st, int phases, const float* reset) {
   using C = CfgFor<T>;
   // bf16 path: the fp32 tail GEMMs on the bf16 MFMA with split operands (AAA_TAIL_SPLIT3=0: fp32 MFMA)
   TailPrecision tail_prec(std::is_same<T, __bf16>::value && env_int("AAA_TAIL_SPLIT3", 1),
@@ -184,6 +184,18 @@ int forward_impl(const Layout& L, const aaa_io* io, hipStream_t st, int phases) 
   const int F = L.F, M = L.B * L.P;
   // fp32 h_t slices for the readout: fp32 path only (bf16 reads XH, readout_h)
   auto hs_out = [&](int t) { return L.esz == 4 ? Wf(L.Hs) + (size_t)t * M * 128 : (float*)nullptr; };
+  // Episode starts (reset != null, fp32): before step t, zeros in the h half of XH slot t for the rows
+  // that enter it from reset() and a masked copy of c_{t-1} (in dC: the BPTT's carry, idle in the
+  // forward) -- Cst slot t keeps the true c_{t-1}, which step t-1's own backward reads (resets.hip).
+  // *cp <- the c_{t-1} the step's cell update reads.
+  auto c_in = [&](int t, const float** cp) -> int {
+    *cp = Wf(L.Cst) + (size_t)t * M * 128;
+    if (!reset) return AAA_OK;
+    HIPCHK(reset_rows(reset + (size_t)t * L.B, L.B, L.P,
+                      ResetZeros{}.add(Wf(L.XH) + (size_t)t * M * 192 + 64, 192, 128), *cp, Wf(L.dC), 128, st));
+    *cp = Wf(L.dC);
+    return AAA_OK;
+  };
 
   {  // conv1 + conv2 over all T*B frames -> XH[:, :, 0:64] of every slot
     TimerScope tim(AAA_TIMER_VISION_FWD, st, (double)F * vision_fwd_flop(L), "conv1 + conv2 (vision encoder)");
@@ -205,9 +217,13 @@ int forward_impl(const Layout& L, const aaa_io* io, hipStream_t st, int phases) 
   }
   // no CORE (aaa_forward_phases, fp32): the recurrence's products are already in
   // Gt / Cst / Hs / XH (aaa_core_import)
-  if (!(phases & AAA_FWD_CORE)) return forward_tail<T>(L, io, st);
+  if (!(phases & AAA_FWD_CORE)) return forward_tail<T>(L, io, st, reset);
   if constexpr (std::is_same<T, float>::value) {
-    if (const int G = f32_frames(L)) {   // one frame-group launch for all T steps, x-part included (recur_f32.h)
+    // (a mask: the frame-group kernels' RST variants where they exist, recur_f32.h f32_fwd_resets, else the
+    // per-step kernels below)
+    int Gf = f32_frames(L);
+    if (reset && Gf && !f32_fwd_resets(f32_split6(), Gf, L.P)) Gf = 0;
+    if (const int G = Gf) {   // one frame-group launch for all T steps, x-part included (recur_f32.h)
       int dev = 0;
       HIPCHK(hipGetDevice(&dev));
       int* rep = pair_report(dev);
@@ -215,17 +231,23 @@ int forward_impl(const Layout& L, const aaa_io* io, hipStream_t st, int phases) 
       RecF32Params rp{(const float*)(pk + L.k_Wf32), (const float*)(pk + L.k_bl), Wf(L.XH), Wf(L.Cst), Wf(L.Hs),
                       Wf(L.Gt), (int*)(ws + L.rflags), rep, pair_budget(L.T), L.T, L.B, L.h, L.w, L.P,
                       io->h0 ? 0 : 1, {}};
+      if (reset) {   // slot 0's h half of the rows that start an episode at step 0: the weight gradient's operand
+        rp.reset = reset;
+        if (io->h0)
+          HIPCHK(reset_rows(reset, L.B, L.P, ResetZeros{}.add(Wf(L.XH) + 64, 192, 128), nullptr, nullptr, 0, st));
+      }
       {
         const bool s6 = f32_split6();
         rp.Wf6 = (const u32x2*)(pk + L.k_Wf6);
         rp.Wf6p = (const u32x4*)(pk + L.k_Wf6p);
         TimerScope tim(AAA_TIMER_FWD_STEP, st, 2.0 * M * 512 * (576.0 * L.T + 1152.0 * (L.T - (io->h0 ? 0 : 1))),
-                       strf("fp32 frame-group [x|h] recurrence%s, %d steps per launch, %d WG per frame [kernel: %s]",
+                       strf("fp32 frame-group [x|h] recurrence%s, %d steps per launch, %d WG per frame [kernel: %s]%s",
                             s6 ? " (bf16x6 split products)" : "", L.T, G,
-                            f32_fwd_presplit(s6, G, L.P) ? "k_convlstm_fwd_f32ps" : "k_convlstm_fwd_f32<"));
+                            f32_fwd_presplit(s6, G, L.P) ? "k_convlstm_fwd_f32ps" : "k_convlstm_fwd_f32<",
+                            reset ? ", resets" : ""));
         HIPCHK(convlstm_fwd_f32(rp, G, st, s6));
       }
-      return forward_tail<T>(L, io, st);
+      return forward_tail<T>(L, io, st, reset);
     }
   }
   // bf16: the x-part rides in each step's GEMM (K over the whole XH slot,
@@ -278,18 +300,20 @@ int forward_impl(const Layout& L, const aaa_io* io, hipStream_t st, int phases) 
         }
       }
       for (int t = 0; t < L.T; ++t) {   // ConvLSTM (attention.py:110-126), x- and h-part together
-        EpiConvLstmFwd<T, GT> ep{Wf(L.Cst) + (size_t)t * M * 128, Wf(L.Cst) + (size_t)(t + 1) * M * 128,
+        const float* cp;
+        if (const int rc = c_in(t, &cp)) return rc;
+        EpiConvLstmFwd<T, GT> ep{cp, Wf(L.Cst) + (size_t)(t + 1) * M * 128,
                                  hs_out(t), Wt(L.XH) + (size_t)(t + 1) * M * 192,
                                  (GT*)(ws + L.Gt) + (size_t)t * M * 512, M, (const float*)(pk + L.k_bl)};
         const int rc = fused_step<T, GT>(WpXH, Wt(L.XH) + (size_t)t * M * 192, L.h, L.w, M, ep, st,
-                                         L.dhs ? Wf(L.dhs) : nullptr);
+                                         L.dhs ? Wf(L.dhs) : nullptr, reset != nullptr);
         if (rc) return rc;
       }
       return AAA_OK;
     };
     const int rc = gates_f16(L.dt, M) ? steps(_Float16{}) : steps(float{});
     if (rc) return rc;
-    return forward_tail<T>(L, io, st);
+    return forward_tail<T>(L, io, st, reset);
   }
   // x-part of the ConvLSTM steps (not recurrent): Gt <- Wx * x_t + b, in
   // chunks of ``cs`` steps on the aux stream; step t waits only for its chunk.
@@ -333,16 +357,18 @@ int forward_impl(const Layout& L, const aaa_io* io, hipStream_t st, int phases) 
   const uint32_t xh_bytes = (uint32_t)((size_t)M * 192 * L.esz);  // one step slice of XH
   for (int t = 0; t < L.T; ++t) {  // ConvLSTM recurrence (attention.py:110-126): h-part only
     if (ax && t % cs == 0) HIPCHK(hipStreamWaitEvent(st, xev[t / cs], 0));   // x-part of steps [t, t+cs) done
+    const float* cp;
+    if (const int rc = c_in(t, &cp)) return rc;
     if (t == 0 && !io->h0) {       // zero state: gates come from the x-part alone
-      HIPCHK(gate_fwd_zx<T>(M, Wf(L.Cst), Wf(L.Gt), Wf(L.Cst) + (size_t)M * 128, hs_out(0), Wt(L.XH) + (size_t)M * 192,
+      HIPCHK(gate_fwd_zx<T>(M, cp, Wf(L.Gt), Wf(L.Cst) + (size_t)M * 128, hs_out(0), Wt(L.XH) + (size_t)M * 192,
                             st));
       continue;
     }
-    EpiConvLstmFwd<T> ep{Wf(L.Cst) + (size_t)t * M * 128, Wf(L.Cst) + (size_t)(t + 1) * M * 128,
+    EpiConvLstmFwd<T> ep{cp, Wf(L.Cst) + (size_t)(t + 1) * M * 128,
                          hs_out(t), Wt(L.XH) + (size_t)(t + 1) * M * 192,
                          Wf(L.Gt) + (size_t)t * M * 512, M};
     const ConvGeo g = ConvGeo{128, 192, 64, L.h, L.w, L.h, L.w, 3, 1, 1, 0}.prep();
-    TimerScope tim(AAA_TIMER_FWD_STEP, st, 2.0 * M * 512 * 1152, strf("%s h-part step (x-part batched), K=1152, tile %d [kernel: EpiConvLstmFwd]", std::is_same<T, float>::value ? "fp32" : "bf16", fwd_tile));
+    TimerScope tim(AAA_TIMER_FWD_STEP, st, 2.0 * M * 512 * 1152, strf("%s h-part step (x-part batched), K=1152, tile %d [kernel: EpiConvLstmFwd]%s", std::is_same<T, float>::value ? "fp32" : "bf16", fwd_tile, reset ? ", resets" : ""));
     const T* WpH = (const T*)(pk + L.k_WpH);
     const T* xh = Wt(L.XH) + (size_t)t * M * 192;
     hipError_t e;
@@ -381,7 +407,7 @@ int forward_impl(const Layout& L, const aaa_io* io, hipStream_t st, int phases) 
     }
     HIPCHK(e);
   }
-  return forward_tail<T>(L, io, st);
+  return forward_tail<T>(L, io, st, reset);
 }
 
 // Stateful policy core (AAA_FLAG_STATEFUL_CORE; the reference's else branch,
@@ -392,7 +418,7 @@ int forward_impl(const Layout& L, const aaa_io* io, hipStream_t st, int phases) 
 // zeros); the LSTMCell epilogue also writes h_t into step t+1's [answer | h]
 // GEMM row, so each step is five small GEMMs and one attention launch.  The
 // heads then run batched over all frames on CH[1..T].
-static int forward_tail_stateful(const Layout& L, const aaa_io* io, hipStream_t st) {
+static int forward_tail_stateful(const Layout& L, const aaa_io* io, hipStream_t st, const float* reset) {
   constexpr int NTF = CF::NT;
   char* ws = (char*)io->workspace;
   const char* pk = (const char*)io->packed;
@@ -413,9 +439,22 @@ static int forward_tail_stateful(const Layout& L, const aaa_io* io, hipStream_t 
     float* q1 = Wf(L.q1s) + f0 * 128;
     float* q2 = Wf(L.q2s) + f0 * qd;
     float* Qt = Wf(L.Qf) + f0 * qd;
+    // Episode starts: zeros in the h half of this step's [answer | h] rows for the rows that enter it
+    // from reset(), and a masked copy of c_{t-1} (in dcc: the backward's carry, idle here); the query
+    // MLP then reads h_{t-1} from those rows, its second copy.  CH / CC slot t keep the true
+    // (h, c)_{t-1}: the heads and step t-1's backward read them.
+    const float* hq = CH + f0 * 256;
+    const float* cprev = CC + f0 * 256;
+    int hq_ld = 256;
+    if (reset) {
+      HIPCHK(reset_rows(reset + f0, B, 1, ResetZeros{}.add(AOX + f0 * 512 + 256, 512, 256), cprev, Wf(L.dcc), 256, st));
+      hq = AOX + f0 * 512 + 256;
+      hq_ld = 512;
+      cprev = Wf(L.dcc);
+    }
     {  // QueryNetwork(prev_output = h_{t-1}) (attention.py:184-198, 331)
       LRf::Params pa{prm + L.poff[Q0W], 256, 128};
-      LRfj::Params pb{CH + f0 * 256, 256, B};
+      LRfj::Params pb{hq, hq_ld, B};
       EpiStoreT<float> ep{q1, 128, 128, B, prm + L.poff[Q0B], 1};
       HIPCHK((tail_gemm(pa, pb, ep, 128, B, 256, st)));
     }
@@ -453,7 +492,7 @@ static int forward_tail_stateful(const Layout& L, const aaa_io* io, hipStream_t 
     {  // policy_core LSTMCell from (h_{t-1}, c_{t-1}) (attention.py:356-358)
       LRf::Params pa{(const float*)(pk + L.k_Wihhp), 512, 1024};
       LRfj::Params pb{AOX + f0 * 512, 512, B};
-      EpiLstmCellFwdS ep{(const float*)(pk + L.k_blc), Wf(L.LG) + f0 * 1024, CC + f0 * 256, CC + (f0 + B) * 256,
+      EpiLstmCellFwdS ep{(const float*)(pk + L.k_blc), Wf(L.LG) + f0 * 1024, cprev, CC + (f0 + B) * 256,
                          CH + (f0 + B) * 256, t + 1 < L.T ? AOX + (f0 + B) * 512 + 256 : nullptr, B};
       HIPCHK((tail_gemm(pa, pb, ep, 1024, B, 512, st)));
     }
@@ -466,7 +505,7 @@ static int forward_tail_stateful(const Layout& L, const aaa_io* io, hipStream_t 
 // Everything after the ConvLSTM: query, attention readout, answer MLP,
 // LSTMCell, heads (all batched over the T*B frames, Q1) and state outputs.
 template <typename T>
-static int forward_tail(const Layout& L, const aaa_io* io, hipStream_t st) {
+static int forward_tail(const Layout& L, const aaa_io* io, hipStream_t st, const float* reset) {
   constexpr int NTF = CF::NT;
   char* ws = (char*)io->workspace;
   const char* pk = (const char*)io->packed;
@@ -474,7 +513,7 @@ static int forward_tail(const Layout& L, const aaa_io* io, hipStream_t st) {
   auto Wf = [&](size_t off) { return (float*)(ws + off); };
   const int F = L.F, P = L.P, M = L.B * L.P;
   if (L.sc) {   // stateful core: the tail runs step by step
-    const int rc = forward_tail_stateful(L, io, st);
+    const int rc = forward_tail_stateful(L, io, st, reset);
     if (rc) return rc;
   } else {
   // constant query (Q1) + fused attention readout over all T*B frames
@@ -545,7 +584,7 @@ template int vision_fwd<__bf16, __bf16>(const Layout&, int, const char*, const f
                                         __bf16*, int, hipStream_t, bool, std::string*);
 template int vision_fwd<__bf16, float>(const Layout&, int, const char*, const float*, const void*, __bf16*, __bf16*,
                                        float*, int, hipStream_t, bool, std::string*);
-template int forward_impl<float>(const Layout&, const aaa_io*, hipStream_t, int);
-template int forward_impl<__bf16>(const Layout&, const aaa_io*, hipStream_t, int);
+template int forward_impl<float>(const Layout&, const aaa_io*, hipStream_t, int, const float*);
+template int forward_impl<__bf16>(const Layout&, const aaa_io*, hipStream_t, int, const float*);
 
 }  // namespace aaa

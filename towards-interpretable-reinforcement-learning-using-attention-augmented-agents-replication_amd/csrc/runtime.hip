@@ -305,6 +305,46 @@ int aaa_backward(const aaa_cfg* cfg, const aaa_io* io, int phases, hipStream_t s
                           : backward_impl<float>(L, io, phases, stream);
 }
 
+// Episode-start masks (include/aaa.h): what a mask cannot go with, refused before the device is touched.
+static int check_reset(const Layout& L, const float* reset, const char* who) {
+  if (!reset) return AAA_OK;
+  if (L.dt == AAA_BF16)
+    return fail(AAA_E_ARG, "%s: an episode-start mask needs an fp32 cfg (the bf16 readout reads h_t from the [x | h] "
+                "operand slots, which a reset zeroes); pass reset = NULL and cut the unroll at episode ends", who);
+  if (!aligned16(reset)) return fail(AAA_E_ALIGN, "%s: the reset mask must be 16-byte aligned", who);
+  return AAA_OK;
+}
+
+int aaa_forward_resets(const aaa_cfg* cfg, const aaa_io* io, int phases, const float* reset, hipStream_t stream) {
+  if (!reset) return aaa_forward_phases(cfg, io, phases, stream);
+  Layout L;
+  int r = build_layout(cfg, L);
+  if (r) return r;
+  if (phases != AAA_FWD_ALL && phases != (AAA_FWD_VISION | AAA_FWD_TAIL))
+    return fail(AAA_E_ARG, "forward phases %d: AAA_FWD_ALL or AAA_FWD_VISION | AAA_FWD_TAIL", phases);
+  if ((r = check_reset(L, reset, "forward_resets"))) return r;
+  if (!(phases & AAA_FWD_CORE))
+    return fail(AAA_E_ARG, "forward_resets: an episode-start mask needs AAA_FWD_CORE (imported ConvLSTM products "
+                "were computed without it)");
+  if ((r = check_device())) return r;
+  if ((r = check_io(L, io, false))) return r;
+  if (!(cfg->flags & AAA_FLAG_DEFER_STRANDED) && (r = pair_check())) return r;
+  return forward_impl<float>(L, io, stream, phases, reset);
+}
+
+int aaa_backward_resets(const aaa_cfg* cfg, const aaa_io* io, int phases, const float* reset, hipStream_t stream) {
+  if (!reset) return aaa_backward(cfg, io, phases, stream);
+  Layout L;
+  int r = build_layout(cfg, L);
+  if (r) return r;
+  if ((r = check_reset(L, reset, "backward_resets"))) return r;
+  if ((r = check_device())) return r;
+  if ((r = check_io(L, io, true))) return r;
+  if (phases & ~AAA_BWD_ALL || !phases) return fail(AAA_E_ARG, "bad phase mask %d", phases);
+  if (!(cfg->flags & AAA_FLAG_DEFER_STRANDED) && (r = pair_check())) return r;
+  return backward_impl<float>(L, io, phases, stream, reset);
+}
+
 int aaa_pair_status(hipStream_t stream, int clear) {
   if (stream && hipStreamSynchronize(stream) != hipSuccess) return fail(AAA_E_LAUNCH, "stream synchronize failed");
   if (!stream && hipDeviceSynchronize() != hipSuccess) return fail(AAA_E_LAUNCH, "device synchronize failed");

@@ -43,7 +43,7 @@ from .attention import SpatialBasis
 from .optim import adam_flat_
 from .parallel import allreduce_buckets, bucket_bounds
 from .runtime import UnrollRunner
-from .vtrace import vtrace_cotangents
+from .vtrace import episode_starts, vtrace_cotangents
 
 
 class Learner:
@@ -86,19 +86,48 @@ class Learner:
             dist.broadcast(self.flat, src=0, group=group)
             self.comm = torch.cuda.Stream(self.device)   # the gradient all-reduces (RCCL) run here
 
-    def step(self, frames, dlogits, dvalues, overlap: bool = True, comm_timing: bool = False):
+    def step(self, frames, dlogits, dvalues, overlap: bool = True, comm_timing: bool = False, reset=None):
         """One learner iteration; returns (logits, values).  With N > 1 ranks the
         gradients are SUM-all-reduced over RCCL on a side stream, issued after
         the CORE and VISION phases (``schedule``): the HEAD+CORE reduction
         overlaps the vision backward and never runs beside a frame-resident
         launch.  ``comm_timing`` records per-bucket events; read them with
-        comm_stats() after a sync."""
-        logits, values = self._forward(frames)
-        self._backward(frames, dlogits, dvalues, overlap, comm_timing)
+        comm_stats() after a sync.  ``reset``: None, or a (T, B) episode-start
+        mask on the device (``UnrollRunner.forward``; fp32 learners)."""
+        reset = self._reset_mask(reset, None, None)
+        logits, values = self._forward(frames, reset)
+        self._backward(frames, dlogits, dvalues, overlap, comm_timing, reset)
         return logits, values
 
+    def _reset_mask(self, reset, done, first):
+        """``reset=`` of the step methods -> None or the (T, B) fp32 device mask: a tensor
+        is passed through; "done" is ``episode_starts(done, first)`` over this unroll's T
+        steps (``done`` of T, or with bootstrap="last" T-1, rows).  No host read."""
+        r = self.runner
+        if reset is None:
+            if first is not None:
+                raise ValueError("first= belongs to reset=\"done\"")
+            return None
+        if isinstance(reset, str):
+            if reset != "done":
+                raise ValueError(f"reset must be None, a (T, B) tensor or \"done\", got {reset!r}")
+            if done is None:
+                raise ValueError("reset=\"done\" needs done")
+            d = torch.as_tensor(done).to(device=self.device, dtype=torch.float32).reshape(-1, r.B)
+            if d.shape[0] == r.T - 1:   # bootstrap="last" inputs of T-1 rows: the last row starts nothing here
+                d = torch.cat([d, torch.zeros(1, r.B, device=self.device)])
+            if d.shape[0] != r.T:
+                raise ValueError(f"reset=\"done\": done must have {r.T} (or {r.T - 1}) rows, got {d.shape[0]}")
+            return episode_starts(d, first)
+        if first is not None:
+            raise ValueError("first= belongs to reset=\"done\"")
+        reset = torch.as_tensor(reset).to(device=self.device, dtype=torch.float32)
+        if tuple(reset.shape) != (r.T, r.B):
+            raise ValueError(f"reset must be {(r.T, r.B)}, got {tuple(reset.shape)}")
+        return reset.contiguous()
+
     def step_vtrace(self, frames, actions, rewards, behaviour_logp=None, done=None, bootstrap=None,
-                    overlap: bool = True, comm_timing: bool = False, **hparams):
+                    overlap: bool = True, comm_timing: bool = False, reset=None, first=None, **hparams):
         """One learner iteration on the V-trace actor-critic loss (vtrace.py;
         include/aaa.h ``aaa_vtrace``): pack -> forward -> the loss kernel, from
         this step's own logits / values into the learner's cotangent buffers ->
@@ -113,6 +142,12 @@ class Learner:
         (``bootstrap="last"`` included: the inputs then have T or T-1 steps'
         worth of rows, of which the first T-1 are used).  ``hparams`` are
         ``vtrace_loss``'s keyword scalars.
+
+        ``reset``: None (the state runs across episode ends, as before), a
+        (T, B) episode-start mask, or ``"done"`` = ``episode_starts(done,
+        first)``: the step after a ``done`` enters from ``reset()``, and
+        ``first`` (B) says which rows start an episode at step 0.  fp32
+        learners (include/aaa.h ``aaa_forward_resets``).
 
         Nothing in the iteration reads the device from the host: there is no
         ``.item()`` and, unlike ``vtrace_loss``, no validation of the action
@@ -144,7 +179,8 @@ class Learner:
         tb = (n * B, T * B)   # the kernel reads the first n steps: a contiguous prefix
         actions, rewards = dev(actions, torch.int32, tb), dev(rewards, torch.float32, tb)
         behaviour_logp, done = dev(behaviour_logp, torch.float32, tb), dev(done, torch.float32, tb)
-        logits, values = self._forward(frames)
+        reset = self._reset_mask(reset, done, first)
+        logits, values = self._forward(frames, reset)
         if last:
             bootstrap = values[T - 1, :, int(hparams.get("value_col", 0))].contiguous()
             dl[n:].zero_()
@@ -154,21 +190,23 @@ class Learner:
         parts = torch.empty(B, 3, device=self.device)
         vtrace_cotangents(logits, values, actions, rewards, behaviour_logp, done, bootstrap, dl, dv, loss=parts,
                           steps=n, **hparams)
-        self._backward(frames, dl, dv, overlap, comm_timing)
+        self._backward(frames, dl, dv, overlap, comm_timing, reset)
         return logits, values, parts
 
-    def _forward(self, frames):
+    def _forward(self, frames, reset=None):
         r = self.runner
         r.pack(self.flat, self.packed)
-        logits, values, _, _, _ = r.forward(self.flat, self.packed, self.basis, frames, self.ws, want_attn=False)
+        logits, values, _, _, _ = r.forward(self.flat, self.packed, self.basis, frames, self.ws, want_attn=False,
+                                            reset=reset)
         return logits, values
 
-    def _backward(self, frames, dlogits, dvalues, overlap, comm_timing):
+    def _backward(self, frames, dlogits, dvalues, overlap, comm_timing, reset=None):
         """The backward half of an iteration: the three phases into ``grads``,
         the all-reduce schedule and the stranded-launch guard."""
         r = self.runner
         if self.world == 1:
-            r.backward(self.flat, self.packed, self.basis, frames, self.ws, dlogits, dvalues, grads=self.grads)
+            r.backward(self.flat, self.packed, self.basis, frames, self.ws, dlogits, dvalues, grads=self.grads,
+                       reset=reset)
             N.pair_flag(self.guard, base=self._pair_base)
             return
         main = torch.cuda.current_stream(self.device)
@@ -176,7 +214,7 @@ class Learner:
         issue = dict(self.schedule[bool(overlap)])
         for phase in (N.BWD_HEAD, N.BWD_CORE, N.BWD_VISION):
             r.backward(self.flat, self.packed, self.basis, frames, self.ws, dlogits, dvalues, grads=self.grads,
-                       phases=phase)
+                       phases=phase, reset=reset)
             if phase == N.BWD_CORE:   # every resident launch of this step is enqueued by now
                 N.pair_flag(self.guard, base=self._pair_base)
             if phase in issue:
@@ -244,15 +282,16 @@ class Learner:
         adam_flat_(self.flat, self.grads, self.exp_avg, self.exp_avg_sq, 0, lr=self.lr, guard=self.guard,
                    step_dev=self.step_dev)
 
-    def train_step(self, frames, dlogits, dvalues, overlap: bool = True):
-        out = self.step(frames, dlogits, dvalues, overlap=overlap)
+    def train_step(self, frames, dlogits, dvalues, overlap: bool = True, reset=None):
+        out = self.step(frames, dlogits, dvalues, overlap=overlap, reset=reset)
         self.optimizer_step()
         return out
 
     def train_step_vtrace(self, frames, actions, rewards, behaviour_logp=None, done=None, bootstrap=None,
-                          overlap: bool = True, **hparams):
+                          overlap: bool = True, reset=None, first=None, **hparams):
         """step_vtrace() followed by the fused Adam update: a complete learner
         iteration, stream-ordered, with no host round trip."""
-        out = self.step_vtrace(frames, actions, rewards, behaviour_logp, done, bootstrap, overlap=overlap, **hparams)
+        out = self.step_vtrace(frames, actions, rewards, behaviour_logp, done, bootstrap, overlap=overlap,
+                               reset=reset, first=first, **hparams)
         self.optimizer_step()
         return out

@@ -84,11 +84,14 @@ class UnrollRunner:
         return io
 
     def forward(self, flat_params, packed, basis, frames, workspace, prev_reward=None, prev_action=None,
-                h0=None, c0=None, want_attn=True, want_state=False, core=None, phases=N.FWD_ALL):
+                h0=None, c0=None, want_attn=True, want_state=False, core=None, phases=N.FWD_ALL, reset=None):
         """Returns (logits, values, attn, hT, cT); a stateful-core runner also
         returns the core state (core_hT, core_cT) (B, 256), starting from
         ``core`` = (h0, c0) or zeros.  ``phases`` = FWD_VISION | FWD_TAIL skips
-        the ConvLSTM recurrence (its products imported first: core_import)."""
+        the ConvLSTM recurrence (its products imported first: core_import).
+        ``reset`` (T, B): rows with reset[t][b] != 0 enter step t from the
+        reset() state (aaa_forward_resets; fp32 runners); pass the same mask
+        to ``backward``."""
         T, B, A = self.T, self.B, self.A
         dev = self.device
         self._check_frames(frames)
@@ -107,7 +110,11 @@ class UnrollRunner:
                          core_hT=torch.empty(B, 256, device=dev), core_cT=torch.empty(B, 256, device=dev))
         io = self._io(params=flat_params, packed=packed, basis=basis, frames=frames,
                       logits=logits, values=values, attn=attn, hT=hT, cT=cT, workspace=workspace, **keep, **extra)
-        if phases == N.FWD_ALL:
+        if reset is not None:
+            keep["reset"] = reset = _mask(reset, (T, B), dev)
+            N.check(self.lib.aaa_forward_resets(ctypes.byref(self.cfg), ctypes.byref(io), int(phases), N.ptr(reset),
+                                                N.stream_ptr(dev)), "forward_resets")
+        elif phases == N.FWD_ALL:
             N.check(self.lib.aaa_forward(ctypes.byref(self.cfg), ctypes.byref(io), N.stream_ptr(dev)), "forward")
         else:
             N.check(self.lib.aaa_forward_phases(ctypes.byref(self.cfg), ctypes.byref(io), int(phases),
@@ -157,9 +164,11 @@ class UnrollRunner:
                                          N.ptr(c), N.ptr(h), N.stream_ptr(self.device)), "core_import")
 
     def backward(self, flat_params, packed, basis, frames, workspace, dlogits, dvalues=None, dhT=None,
-                 dcT=None, grads=None, want_state_grads=False, phases=N.BWD_ALL, dcore=None, want_core_grads=False):
+                 dcT=None, grads=None, want_state_grads=False, phases=N.BWD_ALL, dcore=None, want_core_grads=False,
+                 reset=None):
         """Returns (grads, dh0, dc0); a stateful-core runner also returns the
-        core-state grads (dcore_h0, dcore_c0) when ``want_core_grads``."""
+        core-state grads (dcore_h0, dcore_c0) when ``want_core_grads``.
+        ``reset``: the mask the forward ran with (aaa_backward_resets)."""
         dev = self.device
         B = self.B
         if grads is None:
@@ -177,8 +186,13 @@ class UnrollRunner:
                          dcore_c0=torch.empty(B, 256, device=dev) if want_core_grads else None)
         io = self._io(params=flat_params, packed=packed, basis=basis, frames=frames, workspace=workspace,
                       grads=grads, dh0=dh0, dc0=dc0, **keep, **extra)
-        N.check(self.lib.aaa_backward(ctypes.byref(self.cfg), ctypes.byref(io), phases, N.stream_ptr(dev)),
-                "backward")
+        if reset is not None:
+            keep["reset"] = reset = _mask(reset, (self.T, B), dev)   # alive until the launches are enqueued
+            N.check(self.lib.aaa_backward_resets(ctypes.byref(self.cfg), ctypes.byref(io), phases, N.ptr(reset),
+                                                 N.stream_ptr(dev)), "backward_resets")
+        else:
+            N.check(self.lib.aaa_backward(ctypes.byref(self.cfg), ctypes.byref(io), phases, N.stream_ptr(dev)),
+                    "backward")
         if self.stateful_core:
             return grads, dh0, dc0, extra["dcore_h0"], extra["dcore_c0"]
         return grads, dh0, dc0
@@ -197,6 +211,15 @@ def _check_out(t, shape, dtype=torch.float32):
             or t.device.type != "cuda"):
         raise ValueError(f"expected a contiguous {dtype} device tensor {tuple(shape)}, got "
                          f"{None if t is None else (tuple(t.shape), t.dtype, t.device)}")
+
+
+def _mask(t, shape, device):
+    """An episode-start mask as the library reads it: contiguous fp32 ``shape`` on the device (no host read)."""
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"reset must have shape {tuple(shape)}, got {tuple(t.shape)}")
+    if t.device.type != "cuda":
+        raise RuntimeError("reset must be on the GPU")
+    return t.to(dtype=torch.float32).contiguous()
 
 
 def _f32(t, shape):

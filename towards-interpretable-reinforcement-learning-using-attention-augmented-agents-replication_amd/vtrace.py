@@ -23,11 +23,29 @@ import torch
 
 from . import _native as N
 
-__all__ = ["vtrace_loss", "vtrace_cotangents", "HPARAMS"]
+__all__ = ["vtrace_loss", "vtrace_cotangents", "episode_starts", "HPARAMS"]
 
 # the loss's scalars and their defaults (IMPALA's: clips at 1, baseline cost 0.5, entropy cost 0.01)
 HPARAMS = dict(gamma=0.99, lam=1.0, rho_bar=1.0, c_bar=1.0, pg_rho_bar=1.0, baseline_cost=0.5,
                entropy_cost=0.01, scale=1.0, value_col=0)
+
+
+def episode_starts(done, first=None):
+    """The episode-start mask of an unroll cut out of longer episodes, (T, B)
+    fp32 on ``done``'s device: row 0 is ``first`` (B; zeros when None: the
+    unroll continues the state it is given) and row t is ``done[t - 1]`` -- the
+    step after an episode's last one enters from ``reset()``.  What
+    ``Agent.unroll(reset=)`` and ``Learner.step_vtrace(reset=)`` take
+    (include/aaa.h ``aaa_forward_resets``).  Runs on the device; nothing is
+    read back."""
+    done = torch.as_tensor(done)
+    if done.dim() != 2:
+        raise ValueError(f"episode_starts: done must be (T, B), got {tuple(done.shape)}")
+    out = torch.zeros(done.shape, dtype=torch.float32, device=done.device)
+    if first is not None:
+        out[0] = torch.as_tensor(first).to(device=done.device, dtype=torch.float32).reshape(-1)
+    out[1:] = done[:-1].to(torch.float32)
+    return out
 
 
 def vtrace_cotangents(logits, values, actions, rewards, behaviour_logp, done, bootstrap, dlogits, dvalues,
