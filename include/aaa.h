@@ -632,6 +632,18 @@ int aaa_vision_enc_fwd(const aaa_enc_desc* d, const float* cnn_params, const voi
 int aaa_vision_enc_bwd(const aaa_enc_desc* d, const void* packed, const void* frames, const void* dy2,
                        const void* y1, void* xp, void* dy1, float* cnn_grads, int* fused, void* workspace,
                        hipStream_t stream);
+/* The fp32 learner's encoder forward the same way (vision_fwd<float, float>:
+ * with split products and a geometry the frame-resident kernel takes,
+ * k_vision_fwd_f32, else -- or with AAA_VIS_FRAMES=0 -- the layered launches):
+ * desc dtype must be AAA_F32, flags 0 or AAA_FLAG_FRAMES_U8, out_ld as above;
+ * packed from aaa_vision_cnn_pack with an AAA_F32 aaa_cnn_desc of the same N,
+ * H, W.  frames (N,H,W,3) -> xp (N,H+2,W+2,4) fp32 the zero-bordered RGBx
+ * frames, y1 (N,H1*W1,32) fp32, out (N,h*w,out_ld) fp32 with conv2's output
+ * in columns 0..63 (the others are not written).  Recorded under
+ * AAA_TIMER_VISION_FWD; arguments checked before the device.  Added after
+ * ABI version 11 without a bump (purely additive): probe by name. */
+int aaa_vision_enc_f32_fwd(const aaa_enc_desc* d, const float* cnn_params, const void* packed, const void* frames,
+                           float* xp, float* y1, float* out, hipStream_t stream);
 
 /* Attention readout of F frames (attention.py:319-348: K/V split + spatial
  * basis, logits K.Q, spatial_softmax :235-243, apply_alpha :246-254, answer

@@ -803,11 +803,14 @@ __global__ void k_cast(long n, const TI* __restrict__ src, TO* __restrict__ dst)
 // ------------------------------------------------------------- packing ----
 // Conv weight in the reference's (Cout, Cin, kx, ky) orientation (Q3) ->
 // [Cout][(ky*K + kx)*Cin + ci].
-template <typename T>
-__device__ __forceinline__ void pack_conv_el(int idx, const float* __restrict__ w, int Cin, int K, T* dst) {
+__device__ __forceinline__ float pack_conv_val(int idx, const float* __restrict__ w, int Cin, int K) {
   const int o = idx / (K * K * Cin), r = idx - o * (K * K * Cin);
   const int tap = r / Cin, ci = r - tap * Cin, ky = tap / K, kx = tap - ky * K;
-  dst[idx] = (T)w[((size_t)(o * Cin + ci) * K + kx) * K + ky];
+  return w[((size_t)(o * Cin + ci) * K + kx) * K + ky];
+}
+template <typename T>
+__device__ __forceinline__ void pack_conv_el(int idx, const float* __restrict__ w, int Cin, int K, T* dst) {
+  dst[idx] = (T)pack_conv_val(idx, w, Cin, K);
 }
 template <typename T>
 __global__ void k_pack_conv(const float* __restrict__ w, int Cout, int Cin, int K, T* dst) {
@@ -859,10 +862,13 @@ __global__ void k_pack_conv2_classes(const float* __restrict__ w2, T* dst) {
 }
 
 // conv1 weights with a zero 4th input channel: [32][(ky*8 + kx)*4 + ci]
+__device__ __forceinline__ float pack_conv1_rgbx_val(int idx, const float* __restrict__ w) {
+  const int o = idx >> 8, r = idx & 255, tap = r >> 2, ci = r & 3, ky = tap >> 3, kx = tap & 7;
+  return ci < 3 ? w[((size_t)(o * 3 + ci) * 8 + kx) * 8 + ky] : 0.f;
+}
 template <typename T>
 __device__ __forceinline__ void pack_conv1_rgbx_el(int idx, const float* __restrict__ w, T* dst) {
-  const int o = idx >> 8, r = idx & 255, tap = r >> 2, ci = r & 3, ky = tap >> 3, kx = tap & 7;
-  dst[idx] = ci < 3 ? (T)w[((size_t)(o * 3 + ci) * 8 + kx) * 8 + ky] : (T)0.f;
+  dst[idx] = (T)pack_conv1_rgbx_val(idx, w);
 }
 template <typename T>
 __global__ void k_pack_conv1_rgbx(const float* __restrict__ w, T* dst) {
@@ -1018,13 +1024,45 @@ __global__ void k_pack_f32(F32Pack p) {
 // one launch (each was its own ~5 us launch): conv1 RGBx, conv2, conv2's dgrad
 // classes, the four ConvLSTM layouts and the fp32 tail layouts, one grid-stride
 // pass over their concatenated index ranges.
+// Element (row, k) of a packed fp32 [rows][16 nks] conv weight matrix -> its three bf16 parts (gemm.h
+// split3_bf16's split) in the fragment order k_vision_fwd_f32 reads (vision_f32.h): 16-B fragment
+// ((row / 32 * nks + k / 16) * 3 + part) * 64 + (k / 8 % 2) * 32 + row % 32, element k % 8.
+__device__ __forceinline__ void vis_split_el(float v, int row, int k, int nks, __bf16* dst) {
+  const __bf16 hi = (__bf16)v;
+  const float r = v - (float)hi;
+  const __bf16 mid = (__bf16)r;
+  const __bf16 lo = (__bf16)(r - (float)mid);
+  const size_t o = ((size_t)(((row >> 5) * nks + (k >> 4)) * 3) * 64 + ((k >> 3) & 1) * 32 + (row & 31)) * 8 + (k & 7);
+  dst[o] = hi;
+  dst[o + 512] = mid;
+  dst[o + 1024] = lo;
+}
+__global__ void k_pack_vis_split(const float* __restrict__ c1w, const float* __restrict__ c2w, __bf16* W1s, __bf16* W2s) {
+  const int n1 = 32 * 256, tot = n1 + 64 * 512;
+  for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < tot; idx += gridDim.x * blockDim.x) {
+    if (idx < n1) {
+      vis_split_el(pack_conv1_rgbx_val(idx, c1w), idx >> 8, idx & 255, 16, W1s);
+    } else {
+      const int i = idx - n1;
+      vis_split_el(pack_conv_val(i, c2w, 32, 4), i >> 9, i & 511, 32, W2s);
+    }
+  }
+}
+
 template <typename T>
 __global__ void k_pack_all(PackAll<T> a) {
   const int n1 = 32 * 256, n2 = n1 + 64 * 512, n3 = n2 + 4 * 32 * 256, n4 = n3 + kPackLstmN;
   const int tot = n4 + pack_f32_n(a.f32);
   for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < tot; idx += gridDim.x * blockDim.x) {
-    if (idx < n1) pack_conv1_rgbx_el(idx, a.c1w, a.Wp1);
-    else if (idx < n2) pack_conv_el(idx - n1, a.c2w, 32, 4, a.Wp2);
+    if (idx < n1) {
+      pack_conv1_rgbx_el(idx, a.c1w, a.Wp1);
+      if constexpr (std::is_same<T, float>::value)
+        if (a.W1s) vis_split_el(a.Wp1[idx], idx >> 8, idx & 255, 16, a.W1s);
+    } else if (idx < n2) {
+      pack_conv_el(idx - n1, a.c2w, 32, 4, a.Wp2);
+      if constexpr (std::is_same<T, float>::value)
+        if (a.W2s) vis_split_el(a.Wp2[idx - n1], (idx - n1) >> 9, (idx - n1) & 511, 32, a.W2s);
+    }
     else if (idx < n3) pack_conv2_classes_el(idx - n2, a.c2w, a.WdT2);
     else if (idx < n4) pack_lstm_el(idx - n3, a.lstm, a.WpX, a.WpH, a.bl, a.WdT, a.WpXH);
     else pack_f32_el(idx - n4, a.f32);
@@ -1501,6 +1539,10 @@ template <typename T>
 hipError_t pack_all(const PackAll<T>& a, hipStream_t st) {
   const long n = 32L * 256 + 64 * 512 + 4 * 32 * 256 + kPackLstmN + pack_f32_n(a.f32);
   hipLaunchKernelGGL(k_pack_all<T>, dim3(nblk(n)), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+hipError_t pack_vis_split(const float* c1w, const float* c2w, __bf16* W1s, __bf16* W2s, hipStream_t st) {
+  hipLaunchKernelGGL(k_pack_vis_split, dim3(nblk(32L * 256 + 64 * 512)), dim3(256), 0, st, c1w, c2w, W1s, W2s);
   return hipGetLastError();
 }
 template hipError_t pack_all<float>(const PackAll<float>&, hipStream_t);

@@ -166,6 +166,8 @@ static int cnn_pack_impl(const Layout& L, const float* prm, char* pk, hipStream_
   HIPCHK(pack_conv1_rgbx<T>(prm + L.poff[C0W], (T*)(pk + L.k_Wp1), st));
   HIPCHK(pack_conv<T>(prm + L.poff[C1W], 64, 32, 4, (T*)(pk + L.k_Wp2), st));
   HIPCHK(pack_conv2_classes<T>(prm + L.poff[C1W], (T*)(pk + L.k_WdT2), st));
+  if constexpr (std::is_same<T, float>::value)   // the frame-resident fp32 encoder's pre-split weights
+    HIPCHK(pack_vis_split(prm + L.poff[C0W], prm + L.poff[C1W], (__bf16*)(pk + L.k_W1s), (__bf16*)(pk + L.k_W2s), st));
   return AAA_OK;
 }
 
@@ -496,6 +498,35 @@ int aaa_vision_enc_fwd(const aaa_enc_desc* d, const float* cnn_params, const voi
   std::string ran;
   r = vision_fwd<__bf16, __bf16>(L, L.F, (const char*)packed, cnn_params, frames, (__bf16*)xp, (__bf16*)y1,
                                  (__bf16*)out, d->out_ld, stream, true, &ran);
+  tim.variant += ": " + ran;
+  return r;
+}
+
+// ---- the fp32 (split-product) encoder forward as the learner runs it (checker entry) ----
+int aaa_vision_enc_f32_fwd(const aaa_enc_desc* d, const float* cnn_params, const void* packed, const void* frames,
+                           float* xp, float* y1, float* out, hipStream_t stream) {
+  if (!d) return fail(AAA_E_ARG, "enc desc is NULL");
+  if (d->dtype != AAA_F32) return fail(AAA_E_ARG, "vision_enc_f32: fp32 only (dtype %d)", d->dtype);
+  if (d->N < 1) return fail(AAA_E_ARG, "vision_enc_f32: need N >= 1");
+  if (d->flags & ~AAA_FLAG_FRAMES_U8) return fail(AAA_E_ARG, "vision_enc_f32: flags may hold AAA_FLAG_FRAMES_U8 only");
+  if (d->out_ld < 64 || d->out_ld % 8)
+    return fail(AAA_E_ARG, "vision_enc_f32: out_ld must be >= 64 and a multiple of 8 (got %d)", d->out_ld);
+  const aaa_cfg cfg{d->N, 1, d->H, d->W, 4, 18, d->dtype, d->flags};
+  Layout L;
+  int r = build_layout(&cfg, L, 1);
+  if (r) return r;
+  if ((size_t)L.F * L.P * d->out_ld * 4 >= (size_t(1) << 31))
+    return fail(AAA_E_ARG, "vision_enc_f32: N*h*w*out_ld is above the 2 GiB descriptor range; split N");
+  if (!cnn_params || !packed || !frames || !xp || !y1 || !out)
+    return fail(AAA_E_ARG, "vision_enc_f32_fwd: cnn_params/packed/frames/xp/y1/out must be set");
+  const void* ptrs[] = {cnn_params, packed, frames, xp, y1, out};
+  for (const void* p : ptrs)
+    if (!aligned16(p)) return fail(AAA_E_ALIGN, "buffers must be 16-byte aligned");
+  if ((r = check_device())) return r;
+  TimerScope tim(AAA_TIMER_VISION_FWD, stream, (double)L.F * vision_fwd_flop(L), "conv1 + conv2 (vision encoder)");
+  std::string ran;
+  r = vision_fwd<float, float>(L, L.F, (const char*)packed, cnn_params, frames, xp, y1, out, d->out_ld, stream, true,
+                               &ran);
   tim.variant += ": " + ran;
   return r;
 }

@@ -57,6 +57,8 @@ int build_layout(const aaa_cfg* c, Layout& L, int min_frames) {
   L.k_Wp1 = take(32 * 256 * e);        // RGBx: 4th input channel zero
   L.k_Wp2 = take(64 * 512 * e);
   L.k_WdT2 = take(4 * 32 * 256 * e);   // conv2 dgrad, 4 parity classes
+  L.k_W1s = take(e == 4 ? kVfW1 : 0);  // fp32: conv1 / conv2 pre-split into bf16 parts, fragment order (vision_f32.h)
+  L.k_W2s = take(e == 4 ? kVfW2 : 0);
   L.k_WpX = take(512 * 576 * e);
   L.k_WpH = take(512 * 1152 * e);
   L.k_WpXH = take(512 * 1728 * e);     // [x | h] step operand (fused x-part, bf16 default)

@@ -12,6 +12,9 @@ int pack_impl(const Layout& L, const float* prm, char* pk, hipStream_t st) {
   a.c1w = prm + L.poff[C0W];
   a.c2w = prm + L.poff[C1W];
   a.Wp1 = (T*)(pk + L.k_Wp1); a.Wp2 = (T*)(pk + L.k_Wp2); a.WdT2 = (T*)(pk + L.k_WdT2);
+  if constexpr (std::is_same<T, float>::value) {   // the frame-resident fp32 encoder's pre-split weights (vision_f32.h)
+    a.W1s = (__bf16*)(pk + L.k_W1s); a.W2s = (__bf16*)(pk + L.k_W2s);
+  }
   for (int g = 0; g < 4; ++g) {
     a.lstm.wx[g] = prm + L.poff[XI_W + 3 * g];
     a.lstm.bx[g] = prm + L.poff[XI_B + 3 * g];
@@ -152,6 +155,18 @@ int vision_fwd(const Layout& L, int F, const char* pk, const float* prm, const v
                       prm + L.poff[C1B], xp_full ? Xp : nullptr, Y1, out, out_ld, F, L.H, L.W, L.H1, L.W1, L.h, L.w};
       HIPCHK(L.fu8 ? vision_fwd_frames<uint8_t>(vp, device_cus(), st) : vision_fwd_frames<float>(vp, device_cus(), st));
       if (ran) *ran = "frame-resident conv1 + conv2 [kernel: k_vision_fwd]";
+      return AAA_OK;
+    }
+  }
+  if constexpr (std::is_same<T, float>::value && std::is_same<OT, float>::value) {
+    // fp32 split products: the frame-resident encoder (vision_f32.h), one launch, which also writes the
+    // fp32 Xp and Y1 the layered backward reads; AAA_VIS_FRAMES=0 -> the layered kernels
+    if (f32_split6() && vis_fits(L.H, L.W, L.H1, L.W1, L.h, L.w) && env_int("AAA_VIS_FRAMES", 1)) {
+      VisF32Params vp{frames, (const bf16x8*)(pk + L.k_W1s), prm + L.poff[C0B], (const bf16x8*)(pk + L.k_W2s),
+                      prm + L.poff[C1B], xp_full ? Xp : nullptr, Y1, out, out_ld, F, L.H, L.W, L.H1, L.W1, L.h, L.w};
+      HIPCHK(L.fu8 ? vision_fwd_frames_f32<uint8_t>(vp, device_cus(), st)
+                   : vision_fwd_frames_f32<float>(vp, device_cus(), st));
+      if (ran) *ran = "frame-resident conv1 + conv2 (bf16x6 split products) [kernel: k_vision_fwd_f32]";
       return AAA_OK;
     }
   }

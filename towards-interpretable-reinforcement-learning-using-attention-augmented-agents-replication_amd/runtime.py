@@ -391,6 +391,51 @@ class EncRunner:
         return grads, (None if fused.value else dy1), bool(fused.value)
 
 
+class EncF32Runner:
+    """The fp32 vision encoder forward as a learner step runs it (aaa_vision_enc_f32_fwd:
+    checker entry), over N frames (N,H,W,3) uint8 or fp32.  Every product comes back as
+    the kernels wrote it, ``torch.float32``."""
+
+    SENTINEL = 0x7A5B7A5B   # bit pattern pre-filled into ``out`` (columns 64.. must keep it)
+
+    def __init__(self, N_: int, H: int, W: int, out_ld: int = 192, frames_u8: bool = True, device=None):
+        self.lib = N.load()
+        self.device = torch.device(device if device is not None else "cuda")
+        if self.device.type != "cuda":
+            raise RuntimeError("aaa: the HIP path needs a ROCm GPU tensor device (no CPU fallback)")
+        self.N, self.H, self.W, self.out_ld, self.u8 = N_, H, W, out_ld, frames_u8
+        self.h, self.w = N.grid(H, W)
+        self.H1, self.W1 = (H + 2 - 8) // 4 + 1, (W + 2 - 8) // 4 + 1
+        self.desc = N.EncDesc(N_, H, W, N.F32, N.FLAG_FRAMES_U8 if frames_u8 else 0, out_ld)
+        self.cnn = N.CnnDesc(N_, H, W, N.F32)
+        self.pk_bytes = self.lib.aaa_vision_cnn_packed_bytes(ctypes.byref(self.cnn))
+        if not self.pk_bytes:
+            N.check(-1, "vision_enc_f32 layout")
+
+    def pack(self, cnn_flat):
+        packed = torch.empty(self.pk_bytes, dtype=torch.uint8, device=self.device)
+        N.check(self.lib.aaa_vision_cnn_pack(ctypes.byref(self.cnn), N.ptr(cnn_flat), N.ptr(packed),
+                                             N.stream_ptr(self.device)), "vision_cnn_pack")
+        return packed
+
+    def forward(self, cnn_flat, packed, frames):
+        """-> (xp (N,H+2,W+2,4), y1 (N,H1,W1,32), out (N,h*w,out_ld)) fp32; xp and y1 are
+        pre-filled with NaN and out with SENTINEL, so an element no kernel wrote shows."""
+        dev = self.device
+        want = torch.uint8 if self.u8 else torch.float32
+        if frames.dtype != want or tuple(frames.shape) != (self.N, self.H, self.W, 3):
+            raise ValueError(f"frames must be {want} of shape {(self.N, self.H, self.W, 3)}")
+        frames = frames.to(dev).contiguous()
+        xp = torch.full((self.N, self.H + 2, self.W + 2, 4), float("nan"), device=dev)
+        y1 = torch.full((self.N, self.H1, self.W1, 32), float("nan"), device=dev)
+        out = torch.full((self.N, self.h * self.w, self.out_ld), self.SENTINEL, dtype=torch.int32,
+                         device=dev).view(torch.float32)
+        N.check(self.lib.aaa_vision_enc_f32_fwd(ctypes.byref(self.desc), N.ptr(cnn_flat), N.ptr(packed),
+                                                N.ptr(frames), N.ptr(xp), N.ptr(y1), N.ptr(out), N.stream_ptr(dev)),
+                "vision_enc_f32_fwd")
+        return xp, y1, out
+
+
 class ActorRunner:
     """One environment step of B <= 16 rows on the actor chain (aaa_actor_step:
     six launches sized for small B; fp32, zero-state policy core by default): the acting
