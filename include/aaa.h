@@ -376,6 +376,58 @@ int aaa_adam_step_counted(const aaa_adam_hparams* hp, int* step_dev, const float
                           float* const* exp_avg_sq, float* const* max_exp_avg_sq, const size_t* numel,
                           hipStream_t stream);
 
+/* ---- gradient clipping by global norm (added after ABI 11 without a bump: additive, probe by name) ----
+ * torch.nn.utils.clip_grad_norm_ (norm_type 2) on the device, with no host
+ * read: aaa_grad_norm writes the total norm and the clip coefficient into
+ * ``stats``; aaa_grad_scale applies the coefficient in place (the drop-in), or
+ * aaa_adam_step_clipped folds it into the counted Adam update and skips the
+ * update -- exactly as a non-zero guard does: no parameter or moment written,
+ * *step_dev not advanced -- when a gradient element is inf or NaN.
+ *
+ * The squares are summed in double (the product of two fp32 values is exact
+ * there) in a fixed order without atomics: the result is within N * 2^-53
+ * relative of the exact sum for N elements, and identical buffers give
+ * bit-identical stats, so the replicas of a data-parallel learner clip and
+ * skip alike with no extra collective.
+ *
+ * stats: 4 floats of device memory, 16-byte aligned:
+ *   [0] total 2-norm of all gradients: fp32 of sqrt(double sum of exact squares)
+ *   [1] coefficient: fp32 of min(1, max_norm / (norm + 1e-6)) evaluated in double with IEEE
+ *       semantics as torch.nn.utils.clip_grad_norm_ states it (NaN norm -> NaN, inf norm -> 0,
+ *       max_norm = +inf -> 1: "norm only")
+ *   [2] 1.0f when the norm is not finite -- which, the squares being summed in double, is
+ *       exactly "some gradient element is inf or NaN" -- else 0.0f
+ *   [3] max_norm as fp32 (echo, for logs)
+ * The flag and the coefficient come from the double norm: finite gradients whose norm exceeds
+ * FLT_MAX (two elements near 3e38, say) give [0] = +inf with [2] = 0 and a correct coefficient.
+ * scratch: aaa_grad_norm_scratch_bytes() of device memory, 16-byte aligned
+ * (one double per workgroup; needs no initialisation, and may be reused by
+ * the next call on the same stream).  Tensor i has numel[i] fp32 elements at
+ * grads[i]; the pointer arrays are host memory, as for aaa_adam_step.
+ * ntensors = 0 or all-empty tensors give norm 0, coefficient 1, flag 0.
+ * Refused before the device is touched: AAA_E_ARG for a NULL array, stats,
+ * scratch or step_dev, a NULL tensor pointer with numel > 0, ntensors < 0,
+ * max_norm NaN or <= 0 (+inf is allowed); AAA_E_ALIGN for a stats or scratch
+ * pointer that is not 16-byte aligned.
+ *
+ * Call order on one stream: backward (and the gradient all-reduce) ->
+ * aaa_grad_norm -> aaa_adam_step_clipped with the same stats (or
+ * aaa_grad_scale, then any optimizer). */
+size_t aaa_grad_norm_scratch_bytes(int ntensors, const size_t* numel);   /* 8 B per chunk, >= 16, multiple of 16 */
+int aaa_grad_norm(double max_norm, int ntensors, const float* const* grads, const size_t* numel,
+                  float* stats, void* scratch, hipStream_t stream);
+/* grads[i] *= stats[1] (one fp32 multiply per element, as grad.mul_(coef));
+ * nothing is written when stats[1] is exactly 1.0f. */
+int aaa_grad_scale(const float* stats, int ntensors, float* const* grads, const size_t* numel, hipStream_t stream);
+/* aaa_adam_step_counted on grads[i] * stats[1] (the fp32 product, then the
+ * update unchanged), skipped and not counted when stats[2] != 0 or *guard != 0
+ * (guard may be NULL).  With a coefficient of exactly 1.0f and weight_decay =
+ * 0 the result is bit-identical to aaa_adam_step_counted. */
+int aaa_adam_step_clipped(const aaa_adam_hparams* hp, int* step_dev, const float* guard, const float* stats,
+                          int ntensors, float* const* params, const float* const* grads, float* const* exp_avg,
+                          float* const* exp_avg_sq, float* const* max_exp_avg_sq, const size_t* numel,
+                          hipStream_t stream);
+
 /* ---- REINFORCE loss ----
  * finish_episode's loss (reference main_mp.py:62-77) for B independent
  * episodes of T steps, on device: discounted returns R_t = r_t + gamma R_{t+1}

@@ -38,6 +38,7 @@ EXPORTS = (
     "aaa_vtrace",
     "aaa_forward_resets", "aaa_backward_resets",
     "aaa_vision_enc_f32_fwd",
+    "aaa_grad_norm_scratch_bytes", "aaa_grad_norm", "aaa_grad_scale", "aaa_adam_step_clipped",
 )
 # include/aaa.h enum aaa_timer
 TIMER_FWD_STEP, TIMER_BPTT_STEP, TIMER_CORE_WGRAD, TIMER_ATTN_FWD, TIMER_ATTN_BWD = 0, 1, 2, 3, 4
@@ -176,6 +177,10 @@ def load(path: str = LIB_PATH):
             "aaa_pair_flag": (I, [P, P]),
             "aaa_pair_flag_at": (I, [P, P, P]),
             "aaa_adam_step_counted": (I, [ctypes.POINTER(AdamHP), P, P, I, P, P, P, P, P, P, P]),
+            "aaa_grad_norm_scratch_bytes": (S, [I, P]),
+            "aaa_grad_norm": (I, [ctypes.c_double, I, P, P, P, P, P]),
+            "aaa_grad_scale": (I, [P, I, P, P, P]),
+            "aaa_adam_step_clipped": (I, [ctypes.POINTER(AdamHP), P, P, P, I, P, P, P, P, P, P, P]),
             "aaa_core_elem_bytes": (I, [ctypes.POINTER(Cfg), ctypes.POINTER(I), ctypes.POINTER(I)]),
             "aaa_workspace_region": (I, [ctypes.POINTER(Cfg), I, ctypes.POINTER(ctypes.c_size_t),
                                          ctypes.POINTER(ctypes.c_size_t)]),
@@ -320,14 +325,53 @@ def pair_flag(dst, stream=None, base=None) -> None:
         check(load().aaa_pair_flag_at(dst.data_ptr(), base.data_ptr(), st), "pair_flag_at")
 
 
+def _tensor_table(ts):
+    """(n, host array of the device pointers, host array of the element counts) of a tensor list."""
+    n = len(ts)
+    return (n, (ctypes.c_void_p * max(n, 1))(*[t.data_ptr() for t in ts]),
+            (ctypes.c_size_t * max(n, 1))(*[t.numel() for t in ts]))
+
+
+def grad_norm_scratch_bytes(numels) -> int:
+    """Bytes of scratch aaa_grad_norm needs for tensors of these element counts (host only)."""
+    n = len(numels)
+    return load().aaa_grad_norm_scratch_bytes(n, (ctypes.c_size_t * max(n, 1))(*numels))
+
+
+def grad_norm(max_norm: float, grads, stats, scratch, stream=None) -> None:
+    """Enqueue the global 2-norm of the fp32 device tensors ``grads`` and the clip
+    coefficient for ``max_norm`` into ``stats`` (4 fp32 device elements: norm,
+    coefficient, non-finite flag, max_norm; include/aaa.h aaa_grad_norm).
+    ``scratch``: a device tensor of at least grad_norm_scratch_bytes() bytes.  No host sync."""
+    n, gp, numel = _tensor_table(grads)
+    need = load().aaa_grad_norm_scratch_bytes(n, numel)
+    if scratch.numel() * scratch.element_size() < need:
+        raise ValueError(f"grad_norm: scratch holds {scratch.numel() * scratch.element_size()} bytes, needs {need}")
+    if stats.numel() < 4 or str(stats.dtype) != "torch.float32":
+        raise ValueError("grad_norm: stats must hold 4 fp32 elements")
+    st = stream if stream is not None else stream_ptr(stats.device)
+    check(load().aaa_grad_norm(float(max_norm), n, gp, numel, stats.data_ptr(), scratch.data_ptr(), st), "grad_norm")
+
+
+def grad_scale(stats, grads, stream=None) -> None:
+    """Enqueue ``g *= stats[1]`` in place over the fp32 device tensors ``grads`` (aaa_grad_scale)."""
+    n, gp, numel = _tensor_table(grads)
+    st = stream if stream is not None else stream_ptr(stats.device)
+    check(load().aaa_grad_scale(stats.data_ptr(), n, gp, numel, st), "grad_scale")
+
+
 def adam_step(hp: AdamHP, step: int, params, grads, exp_avg, exp_avg_sq, max_exp_avg_sq=None, stream=None,
-              guard=None, step_dev=None) -> None:
+              guard=None, step_dev=None, clip=None) -> None:
     """One fused Adam launch over lists of same-length fp32 device tensors
     (aaa_adam_step; with ``guard``, a one-element fp32 device tensor,
     aaa_adam_step_guarded: no update when guard != 0; with ``step_dev``, a
     one-element int32 device tensor, aaa_adam_step_counted: ``step`` is
     ignored, the update is number step_dev + 1 and step_dev advances on the
-    device only when the update was applied)."""
+    device only when the update was applied; with ``clip``, grad_norm()'s
+    stats tensor, aaa_adam_step_clipped: the counted update on grad *
+    clip[1], skipped when clip[2] != 0 -- it needs ``step_dev``)."""
+    if clip is not None and step_dev is None:
+        raise ValueError("adam_step: clip= needs step_dev (aaa_adam_step_clipped is the counted update)")
     n = len(params)
     VP = ctypes.c_void_p * max(n, 1)
     def arr(ts):
@@ -339,6 +383,12 @@ def adam_step(hp: AdamHP, step: int, params, grads, exp_avg, exp_avg_sq, max_exp
     st = stream if stream is not None else stream_ptr()
     if step_dev is not None:
         assert step_dev.numel() == 1 and step_dev.is_cuda and str(step_dev.dtype) == "torch.int32"
+    if clip is not None:
+        check(load().aaa_adam_step_clipped(ctypes.byref(hp), step_dev.data_ptr(),
+                                           guard.data_ptr() if guard is not None else None, clip.data_ptr(), n,
+                                           arr(params), arr(grads), arr(exp_avg), arr(exp_avg_sq), mx, numel, st),
+              "adam_step_clipped")
+    elif step_dev is not None:
         check(load().aaa_adam_step_counted(ctypes.byref(hp), step_dev.data_ptr(),
                                            guard.data_ptr() if guard is not None else None, n, arr(params),
                                            arr(grads), arr(exp_avg), arr(exp_avg_sq), mx, numel, st),

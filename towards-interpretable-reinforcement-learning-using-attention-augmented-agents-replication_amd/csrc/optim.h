@@ -25,11 +25,26 @@ struct AdamHost {
   const float* guard = nullptr;   // device float: skip the update when != 0
   int* step_dev = nullptr;        // device step counter (aaa_adam_step_counted): step = *step_dev + 1,
                                   // advanced in stream order only when the update was applied
+  const float* stats = nullptr;   // aaa_grad_norm's stats (aaa_adam_step_clipped): g = grad * stats[1], and
+                                  // no update (nor count) when stats[2] != 0
+};
+
+// aaa_grad_norm / aaa_grad_scale: the gradients alone, chunked as AdamTable is
+struct GradTable {
+  float* g[kAdamMaxTensors];          // read-only for the norm
+  size_t numel[kAdamMaxTensors];
+  int chunk0[kAdamMaxTensors];
+  unsigned char vec[kAdamMaxTensors]; // pointer 16-byte aligned
+  int n;
 };
 
 int adam_chunks(size_t numel);
 // advance: count this update on h.step_dev after the launch (the last table of a step)
 hipError_t adam_launch(const AdamTable& tab, int nchunks, const AdamHost& h, hipStream_t st, bool advance);
+// one double per workgroup to scratch[chunk_base + workgroup]; then one workgroup over all nchunks partials
+hipError_t gradsq_launch(const GradTable& tab, int nchunks, int chunk_base, double* scratch, hipStream_t st);
+hipError_t gradsq_finish_launch(const double* scratch, int nchunks, double max_norm, float* stats, hipStream_t st);
+hipError_t grad_scale_launch(const GradTable& tab, int nchunks, const float* stats, hipStream_t st);
 hipError_t pair_flag_launch(const int* report, int* base, float* dst, hipStream_t st);
 
 // loss.hip: REINFORCE (finish_episode) loss + logits cotangent, one workgroup per episode

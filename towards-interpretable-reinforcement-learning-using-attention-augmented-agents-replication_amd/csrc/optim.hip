@@ -28,6 +28,7 @@ struct AdamScalars {
   int amsgrad, maximize;
   const float* guard;   // skip the whole update when *guard != 0 (aaa_adam_step_guarded), or nullptr
   const int* step_dev;  // device step counter (aaa_adam_step_counted), or nullptr: the scalars above hold
+  const float* stats;   // k_gradsq_finish's stats (aaa_adam_step_clipped), read only by k_adam<true>
   double lr, beta1, beta2;   // the host's doubles (torch's Python floats), read only with step_dev
 };
 
@@ -56,11 +57,11 @@ constexpr int kAdamThreads = 256;
 constexpr int kAdamVec = 4;                                   // floats per 16-byte access
 constexpr int kAdamChunk = kAdamThreads * kAdamVec * 4;       // elements per workgroup
 
-// Workgroup -> (tensor, chunk) through the chunk prefix table; tensors whose
-// pointers are all 16-byte aligned use 16-byte vectors, the rest scalars.
-__global__ void __launch_bounds__(kAdamThreads) k_adam(AdamTable tab, AdamScalars s) {
-  if (s.guard && *s.guard != 0.f) return;   // gradients of a stranded launch: no update on any rank
-  if (s.step_dev) adam_device_step(s);
+// One workgroup's chunk of one tensor.  kScale: the gradient is grad * coef,
+// rounded to fp32 before anything else reads it (grad.mul_(coef)): __fmul_rn
+// keeps the product out of a contraction with adam_elem's first add.
+template <bool kScale>
+__device__ __forceinline__ void adam_chunk(const AdamTable& tab, const AdamScalars& s, float coef) {
   const int b = blockIdx.x;
   int t = 0;
   while (t + 1 < tab.n && tab.chunk0[t + 1] <= b) ++t;
@@ -72,6 +73,7 @@ __global__ void __launch_bounds__(kAdamThreads) k_adam(AdamTable tab, AdamScalar
   float* __restrict__ V = tab.v[t];
   float* __restrict__ X = tab.vmax[t];
   const bool vec = tab.vec[t];
+  auto grad = [&](float g) { return kScale ? __fmul_rn(g, coef) : g; };
   if (vec) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -85,7 +87,7 @@ __global__ void __launch_bounds__(kAdamThreads) k_adam(AdamTable tab, AdamScalar
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           float pe = p[e], me = m[e], ve = v[e], xe = x[e];
-          adam_elem(pe, g[e], me, ve, X ? &xe : nullptr, s);
+          adam_elem(pe, grad(g[e]), me, ve, X ? &xe : nullptr, s);
           p[e] = pe; m[e] = me; v[e] = ve; x[e] = xe;
         }
         *reinterpret_cast<f32x4*>(P + i) = p;
@@ -93,20 +95,40 @@ __global__ void __launch_bounds__(kAdamThreads) k_adam(AdamTable tab, AdamScalar
         *reinterpret_cast<f32x4*>(V + i) = v;
         if (X) *reinterpret_cast<f32x4*>(X + i) = x;
       } else {
-        for (size_t j = i; j < n; ++j) adam_elem(P[j], G[j], M[j], V[j], X ? X + j : nullptr, s);
+        for (size_t j = i; j < n; ++j) adam_elem(P[j], grad(G[j]), M[j], V[j], X ? X + j : nullptr, s);
       }
     }
   } else {
     for (int r = 0; r < kAdamVec * 4; ++r) {
       const size_t j = base + (size_t)r * kAdamThreads + threadIdx.x;
-      if (j < n) adam_elem(P[j], G[j], M[j], V[j], X ? X + j : nullptr, s);
+      if (j < n) adam_elem(P[j], grad(G[j]), M[j], V[j], X ? X + j : nullptr, s);
     }
   }
 }
 
-// After k_adam in stream order: count the update iff the guard let it through.
-__global__ void k_adam_advance(const float* __restrict__ guard, int* __restrict__ step_dev) {
-  if (threadIdx.x == 0 && !(guard && *guard != 0.f)) step_dev[0] = step_dev[0] + 1;
+// Workgroup -> (tensor, chunk) through the chunk prefix table; tensors whose
+// pointers are all 16-byte aligned use 16-byte vectors, the rest scalars.
+// kClip (aaa_adam_step_clipped): no update either when the gradient norm was
+// not finite (stats[2]); otherwise the gradient is grad * stats[1].  The
+// coefficient is the same for the whole grid, so a step the clip leaves alone
+// (exactly 1.0f) takes the unscaled path.
+template <bool kClip>
+__global__ void __launch_bounds__(kAdamThreads) k_adam(AdamTable tab, AdamScalars s) {
+  if (s.guard && *s.guard != 0.f) return;   // gradients of a stranded launch: no update on any rank
+  float coef = 1.f;
+  if (kClip) {
+    if (s.stats[2] != 0.f) return;          // an inf or NaN gradient: no update on any rank
+    coef = s.stats[1];
+  }
+  if (s.step_dev) adam_device_step(s);
+  if (kClip && coef != 1.f) adam_chunk<true>(tab, s, coef);
+  else adam_chunk<false>(tab, s, 1.f);
+}
+
+// After k_adam in stream order: count the update iff the guard (and, clipped, the norm's flag) let it through.
+__global__ void k_adam_advance(const float* __restrict__ guard, const float* __restrict__ stats,
+                               int* __restrict__ step_dev) {
+  if (threadIdx.x == 0 && !(guard && *guard != 0.f) && !(stats && stats[2] != 0.f)) step_dev[0] = step_dev[0] + 1;
 }
 
 hipError_t adam_launch(const AdamTable& tab, int nchunks, const AdamHost& h, hipStream_t st, bool advance) {
@@ -122,11 +144,129 @@ hipError_t adam_launch(const AdamTable& tab, int nchunks, const AdamHost& h, hip
   s.maximize = h.maximize;
   s.guard = h.guard;
   s.step_dev = h.step_dev;
+  s.stats = h.stats;
   s.lr = h.lr;
   s.beta1 = h.beta1;
   s.beta2 = h.beta2;
-  if (nchunks > 0) hipLaunchKernelGGL(k_adam, dim3(nchunks), dim3(kAdamThreads), 0, st, tab, s);
-  if (h.step_dev && advance) hipLaunchKernelGGL(k_adam_advance, dim3(1), dim3(64), 0, st, h.guard, h.step_dev);
+  if (nchunks > 0) {
+    if (h.stats) hipLaunchKernelGGL(k_adam<true>, dim3(nchunks), dim3(kAdamThreads), 0, st, tab, s);
+    else hipLaunchKernelGGL(k_adam<false>, dim3(nchunks), dim3(kAdamThreads), 0, st, tab, s);
+  }
+  if (h.step_dev && advance)
+    hipLaunchKernelGGL(k_adam_advance, dim3(1), dim3(64), 0, st, h.guard, h.stats, h.step_dev);
+  return hipGetLastError();
+}
+
+// ---- global gradient norm (aaa_grad_norm) ----
+// sum g^2 over every tensor, in double: the product of two fp32 values is
+// exact there, so the only rounding is the summation's (N * 2^-53 relative,
+// far inside half an fp32 ulp of the norm for any order).  The order is fixed
+// all the same -- per thread, then the wave's butterfly, then the 4 waves,
+// then the partials -- so identical buffers give bit-identical stats: the
+// ranks of a data-parallel learner decide alike without a collective.  No
+// atomics; one double per workgroup goes to scratch[chunk].
+__device__ __forceinline__ double wg_sum_fixed(double v, double* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);   // a + b == b + a: every lane holds the same sum
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) red[wave] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+__global__ void __launch_bounds__(kAdamThreads) k_gradsq(GradTable tab, double* __restrict__ scratch, int chunk_base) {
+  __shared__ double red[kAdamThreads / 64];
+  const int b = blockIdx.x;
+  int t = 0;
+  while (t + 1 < tab.n && tab.chunk0[t + 1] <= b) ++t;
+  const size_t n = tab.numel[t];
+  const size_t base = (size_t)(b - tab.chunk0[t]) * kAdamChunk;
+  const float* __restrict__ G = tab.g[t];
+  double acc = 0.0;
+  if (tab.vec[t]) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const size_t i = base + ((size_t)r * kAdamThreads + threadIdx.x) * kAdamVec;
+      if (i + kAdamVec <= n) {
+        const f32x4 g = *reinterpret_cast<const f32x4*>(G + i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc += (double)g[e] * (double)g[e];
+      } else {
+        for (size_t j = i; j < n; ++j) acc += (double)G[j] * (double)G[j];
+      }
+    }
+  } else {
+    for (int r = 0; r < kAdamVec * 4; ++r) {
+      const size_t j = base + (size_t)r * kAdamThreads + threadIdx.x;
+      if (j < n) acc += (double)G[j] * (double)G[j];
+    }
+  }
+  const double tot = wg_sum_fixed(acc, red);
+  if (threadIdx.x == 0) scratch[(size_t)chunk_base + b] = tot;
+}
+
+// One workgroup: the partials in a fixed order, then the four stats (include/aaa.h).
+__global__ void __launch_bounds__(kAdamThreads) k_gradsq_finish(const double* __restrict__ scratch, int nchunks,
+                                                                 double max_norm, float* __restrict__ stats) {
+  __shared__ double red[kAdamThreads / 64];
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < nchunks; i += kAdamThreads) acc += scratch[i];
+  const double norm = sqrt(wg_sum_fixed(acc, red));
+  if (threadIdx.x == 0) {
+    // torch.nn.utils.clip_grad_norm_: clamp(max_norm / (total_norm + 1e-6), max=1.0); a NaN stays NaN
+    const double c = max_norm / (norm + 1e-6);
+    f32x4 o;
+    o[0] = (float)norm;
+    o[1] = (float)(c > 1.0 ? 1.0 : c);
+    o[2] = isfinite(norm) ? 0.f : 1.f;
+    o[3] = (float)max_norm;
+    *reinterpret_cast<f32x4*>(stats) = o;
+  }
+}
+
+hipError_t gradsq_launch(const GradTable& tab, int nchunks, int chunk_base, double* scratch, hipStream_t st) {
+  if (nchunks > 0) hipLaunchKernelGGL(k_gradsq, dim3(nchunks), dim3(kAdamThreads), 0, st, tab, scratch, chunk_base);
+  return hipGetLastError();
+}
+
+hipError_t gradsq_finish_launch(const double* scratch, int nchunks, double max_norm, float* stats, hipStream_t st) {
+  hipLaunchKernelGGL(k_gradsq_finish, dim3(1), dim3(kAdamThreads), 0, st, scratch, nchunks, max_norm, stats);
+  return hipGetLastError();
+}
+
+// g *= stats[1] in place; nothing to do (and nothing written) when the clip left the step alone.
+__global__ void __launch_bounds__(kAdamThreads) k_grad_scale(GradTable tab, const float* __restrict__ stats) {
+  const float coef = stats[1];
+  if (coef == 1.f) return;
+  const int b = blockIdx.x;
+  int t = 0;
+  while (t + 1 < tab.n && tab.chunk0[t + 1] <= b) ++t;
+  const size_t n = tab.numel[t];
+  const size_t base = (size_t)(b - tab.chunk0[t]) * kAdamChunk;
+  float* __restrict__ G = tab.g[t];
+  if (tab.vec[t]) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const size_t i = base + ((size_t)r * kAdamThreads + threadIdx.x) * kAdamVec;
+      if (i + kAdamVec <= n) {
+        f32x4 g = *reinterpret_cast<const f32x4*>(G + i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) g[e] = g[e] * coef;
+        *reinterpret_cast<f32x4*>(G + i) = g;
+      } else {
+        for (size_t j = i; j < n; ++j) G[j] = G[j] * coef;
+      }
+    }
+  } else {
+    for (int r = 0; r < kAdamVec * 4; ++r) {
+      const size_t j = base + (size_t)r * kAdamThreads + threadIdx.x;
+      if (j < n) G[j] = G[j] * coef;
+    }
+  }
+}
+
+hipError_t grad_scale_launch(const GradTable& tab, int nchunks, const float* stats, hipStream_t st) {
+  if (nchunks > 0) hipLaunchKernelGGL(k_grad_scale, dim3(nchunks), dim3(kAdamThreads), 0, st, tab, stats);
   return hipGetLastError();
 }
 

@@ -385,21 +385,25 @@ int aaa_adam_step(const aaa_adam_hparams* hp, long step, int ntensors, float* co
                                stream);
 }
 
+// who: the entry's message prefix; stats: aaa_adam_step_clipped's, or nullptr
 static int adam_impl(const aaa_adam_hparams* hp, long step, int* step_dev, const float* guard, int ntensors,
                      float* const* params, const float* const* grads, float* const* exp_avg,
                      float* const* exp_avg_sq, float* const* max_exp_avg_sq, const size_t* numel,
-                     hipStream_t stream) {
+                     hipStream_t stream, const char* who = "adam", const float* stats = nullptr) {
   if (!hp || ntensors < 0 || (ntensors > 0 && (!params || !grads || !exp_avg || !exp_avg_sq || !numel)))
-    return fail(AAA_E_ARG, "adam: NULL argument");
-  if (!step_dev && step < 1) return fail(AAA_E_ARG, "adam: step must be >= 1 (got %ld)", step);
-  if (hp->amsgrad && !max_exp_avg_sq) return fail(AAA_E_ARG, "adam: amsgrad needs max_exp_avg_sq");
+    return fail(AAA_E_ARG, "%s: NULL argument", who);
+  if (!step_dev && step < 1) return fail(AAA_E_ARG, "%s: step must be >= 1 (got %ld)", who, step);
+  if (hp->amsgrad && !max_exp_avg_sq) return fail(AAA_E_ARG, "%s: amsgrad needs max_exp_avg_sq", who);
   if (!(hp->lr >= 0.0) || !(hp->eps >= 0.0) || !(hp->beta1 >= 0.0 && hp->beta1 < 1.0) ||
       !(hp->beta2 >= 0.0 && hp->beta2 < 1.0) || !(hp->weight_decay >= 0.0))
-    return fail(AAA_E_ARG, "adam: invalid hyper-parameters");
+    return fail(AAA_E_ARG, "%s: invalid hyper-parameters", who);
+  for (int t = 0; t < ntensors; ++t)   // every refusal before the device
+    if (numel[t] && (!params[t] || !grads[t] || !exp_avg[t] || !exp_avg_sq[t] || (hp->amsgrad && !max_exp_avg_sq[t])))
+      return fail(AAA_E_ARG, "%s: NULL pointer for tensor %d", who, t);
   int r = check_device();
   if (r) return r;
   AdamHost h{hp->lr, hp->beta1, hp->beta2, hp->eps, hp->weight_decay, step_dev ? 1 : step, hp->amsgrad ? 1 : 0,
-             hp->maximize ? 1 : 0, guard, step_dev};
+             hp->maximize ? 1 : 0, guard, step_dev, stats};
   for (int t0 = 0; t0 < ntensors; t0 += kAdamMaxTensors) {
     AdamTable tab;
     memset(&tab, 0, sizeof tab);
@@ -407,8 +411,6 @@ static int adam_impl(const aaa_adam_hparams* hp, long step, int* step_dev, const
     for (int t = t0; t < std::min(ntensors, t0 + kAdamMaxTensors); ++t) {
       if (numel[t] == 0) continue;
       const int i = tab.n++;
-      if (!params[t] || !grads[t] || !exp_avg[t] || !exp_avg_sq[t] || (h.amsgrad && !max_exp_avg_sq[t]))
-        return fail(AAA_E_ARG, "adam: NULL pointer for tensor %d", t);
       tab.p[i] = params[t]; tab.g[i] = grads[t]; tab.m[i] = exp_avg[t]; tab.v[i] = exp_avg_sq[t];
       tab.vmax[i] = h.amsgrad ? max_exp_avg_sq[t] : nullptr;
       tab.numel[i] = numel[t];
@@ -416,7 +418,7 @@ static int adam_impl(const aaa_adam_hparams* hp, long step, int* step_dev, const
       tab.vec[i] = aligned16(params[t]) && aligned16(grads[t]) && aligned16(exp_avg[t]) && aligned16(exp_avg_sq[t]) &&
                    (!tab.vmax[i] || aligned16(tab.vmax[i]));
       const long c = adam_chunks(numel[t]);
-      if (nch + c > (1L << 30)) return fail(AAA_E_ARG, "adam: tensor %d too large", t);
+      if (nch + c > (1L << 30)) return fail(AAA_E_ARG, "%s: tensor %d too large", who, t);
       nch += (int)c;
     }
     HIPCHK(adam_launch(tab, nch, h, stream, t0 + kAdamMaxTensors >= ntensors));
@@ -440,6 +442,92 @@ int aaa_adam_step_counted(const aaa_adam_hparams* hp, int* step_dev, const float
   if (!step_dev) return fail(AAA_E_ARG, "adam: NULL step counter");
   return adam_impl(hp, 0, step_dev, guard, ntensors, params, grads, exp_avg, exp_avg_sq, max_exp_avg_sq, numel,
                    stream);
+}
+
+// ---- gradient clipping by global norm ----
+// The argument checks of aaa_grad_norm / aaa_grad_scale, all before the device; *total: the chunk count.
+static int clip_check_grads(const char* who, int ntensors, const float* const* grads, const size_t* numel, long* total) {
+  if (ntensors < 0) return fail(AAA_E_ARG, "clip: %s: ntensors must be >= 0 (got %d)", who, ntensors);
+  if (ntensors > 0 && (!grads || !numel)) return fail(AAA_E_ARG, "clip: %s: NULL grads or numel array", who);
+  long nch = 0;
+  for (int t = 0; t < ntensors; ++t) {
+    if (numel[t] == 0) continue;
+    if (!grads[t]) return fail(AAA_E_ARG, "clip: %s: NULL pointer for tensor %d", who, t);
+    nch += adam_chunks(numel[t]);
+    if (nch > (1L << 30)) return fail(AAA_E_ARG, "clip: %s: tensor %d too large", who, t);
+  }
+  *total = nch;
+  return AAA_OK;
+}
+
+// Tensors [t0, t0 + kAdamMaxTensors) as one kernel table; returns its chunk count.
+static int clip_table(GradTable& tab, int t0, int ntensors, const float* const* grads, const size_t* numel) {
+  memset(&tab, 0, sizeof tab);
+  int nch = 0;
+  for (int t = t0; t < std::min(ntensors, t0 + kAdamMaxTensors); ++t) {
+    if (numel[t] == 0) continue;
+    const int i = tab.n++;
+    tab.g[i] = const_cast<float*>(grads[t]);
+    tab.numel[i] = numel[t];
+    tab.chunk0[i] = nch;
+    tab.vec[i] = aligned16(grads[t]);
+    nch += adam_chunks(numel[t]);
+  }
+  return nch;
+}
+
+size_t aaa_grad_norm_scratch_bytes(int ntensors, const size_t* numel) {
+  size_t nch = 0;
+  for (int t = 0; numel && t < ntensors; ++t) nch += (size_t)adam_chunks(numel[t]);
+  return std::max<size_t>(16, (nch * sizeof(double) + 15) & ~(size_t)15);
+}
+
+int aaa_grad_norm(double max_norm, int ntensors, const float* const* grads, const size_t* numel, float* stats,
+                  void* scratch, hipStream_t stream) {
+  long total = 0;
+  int r = clip_check_grads("grad_norm", ntensors, grads, numel, &total);
+  if (r) return r;
+  if (!stats || !scratch) return fail(AAA_E_ARG, "clip: grad_norm: NULL stats or scratch");
+  if (!(max_norm > 0.0)) return fail(AAA_E_ARG, "clip: grad_norm: max_norm must be positive (+inf: norm only)");
+  if (!aligned16(stats) || !aligned16(scratch))
+    return fail(AAA_E_ALIGN, "clip: grad_norm: stats and scratch must be 16-byte aligned");
+  r = check_device();
+  if (r) return r;
+  int base = 0;   // the partial index runs on through the tables
+  for (int t0 = 0; t0 < ntensors; t0 += kAdamMaxTensors) {
+    GradTable tab;
+    const int nch = clip_table(tab, t0, ntensors, grads, numel);
+    HIPCHK(gradsq_launch(tab, nch, base, (double*)scratch, stream));
+    base += nch;
+  }
+  HIPCHK(gradsq_finish_launch((const double*)scratch, base, max_norm, stats, stream));
+  return AAA_OK;
+}
+
+int aaa_grad_scale(const float* stats, int ntensors, float* const* grads, const size_t* numel, hipStream_t stream) {
+  long total = 0;
+  int r = clip_check_grads("grad_scale", ntensors, grads, numel, &total);
+  if (r) return r;
+  if (!stats) return fail(AAA_E_ARG, "clip: grad_scale: NULL stats");
+  if (!aligned16(stats)) return fail(AAA_E_ALIGN, "clip: grad_scale: stats must be 16-byte aligned");
+  r = check_device();
+  if (r) return r;
+  for (int t0 = 0; t0 < ntensors; t0 += kAdamMaxTensors) {
+    GradTable tab;
+    const int nch = clip_table(tab, t0, ntensors, grads, numel);
+    HIPCHK(grad_scale_launch(tab, nch, stats, stream));
+  }
+  return AAA_OK;
+}
+
+int aaa_adam_step_clipped(const aaa_adam_hparams* hp, int* step_dev, const float* guard, const float* stats,
+                          int ntensors, float* const* params, const float* const* grads, float* const* exp_avg,
+                          float* const* exp_avg_sq, float* const* max_exp_avg_sq, const size_t* numel,
+                          hipStream_t stream) {
+  if (!step_dev || !stats) return fail(AAA_E_ARG, "clip: adam: NULL step counter or stats");
+  if (!aligned16(stats)) return fail(AAA_E_ALIGN, "clip: adam: stats must be 16-byte aligned");
+  return adam_impl(hp, 0, step_dev, guard, ntensors, params, grads, exp_avg, exp_avg_sq, max_exp_avg_sq, numel,
+                   stream, "clip: adam", stats);
 }
 
 int aaa_reinforce(int T, int B, int A, const float* logits, const int* actions, const float* rewards, double gamma,

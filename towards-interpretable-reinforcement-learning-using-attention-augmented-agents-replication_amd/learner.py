@@ -26,7 +26,10 @@ all-reduce, so every rank sees any rank's timeout, and the fused Adam skips
 the update on the device when it is non-zero -- gradients of a stranded
 launch never reach the parameters, with no host sync.  The Adam step count
 lives on the device too (aaa_adam_step_counted), advanced only by an applied
-update, so a skipped step leaves the bias corrections where they were.  The
+update, so a skipped step leaves the bias corrections where they were.
+``max_grad_norm`` clips the gradients by their global norm inside that update
+(aaa_grad_norm, aaa_adam_step_clipped) and skips it the same way when a
+gradient is inf or NaN.  The
 learner's runner defers the API's own stranded check (AAA_FLAG_DEFER_STRANDED):
 no rank can raise between its collectives and leave its peers waiting in an
 unmatched all-reduce; ``check_health()`` raises after the step instead.
@@ -49,7 +52,7 @@ from .vtrace import episode_starts, vtrace_cotangents
 class Learner:
     def __init__(self, B: int, T: int, H: int = 84, W: int = 84, nq: int = 4, A: int = 18,
                  dtype: str = "fp32", device=None, seed: int = 0, group=None, lr: float = 1e-3,
-                 frames_u8: bool = False):
+                 frames_u8: bool = False, max_grad_norm: float | None = None):
         self.runner = r = UnrollRunner(B, T, H, W, nq, A, dtype, device, frames_u8=frames_u8, defer_stranded=True)
         self.device = r.device
         params = detinit.deterministic_params(seed, A, nq)
@@ -71,6 +74,14 @@ class Learner:
         self.exp_avg = torch.zeros_like(self.grads)
         self.exp_avg_sq = torch.zeros_like(self.grads)
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=self.device)   # Adam updates applied
+        # clip by global norm (optimizer_step reads the attribute, so it can be toggled between steps):
+        # [norm, coefficient, non-finite flag, max_norm] of the last clipped step, and the norm's partials
+        self.max_grad_norm = max_grad_norm
+        self.grad_stats = torch.zeros(4, device=self.device)
+        self._clip_scratch = None
+        if hasattr(N.load(), "aaa_grad_norm"):   # (an older A/B library under AAA_LIB has no clipping entries)
+            self._clip_scratch = torch.empty(N.grad_norm_scratch_bytes([r.n_params]) // 8, dtype=torch.float64,
+                                             device=self.device)
         self.basis = SpatialBasis(r.h, r.w).S.to(self.device).contiguous()
         self._vt = None   # step_vtrace's (dlogits, dvalues), allocated on its first call
         self.group = group
@@ -278,9 +289,32 @@ class Learner:
     def optimizer_step(self):
         """Adam (lr=1e-3, torch defaults; main_mp.py:92) on the flat params, one
         launch, skipped on the device when the guard slot is non-zero (and then
-        not counted: the device step counter advances only on an update)."""
+        not counted: the device step counter advances only on an update).
+
+        With ``max_grad_norm`` set, the gradients are first clipped by their
+        global 2-norm, on the device: the norm of ``grads`` (under data
+        parallelism the SUM-all-reduced ones -- _backward has made this stream
+        wait for the comm stream; the guard slot is not part of it) goes to
+        ``grad_stats``, and the update runs on ``grads * coefficient`` inside
+        the same fused launch.  A norm that is not finite -- some gradient
+        element is inf or NaN -- skips the update exactly as the guard does."""
+        if self.max_grad_norm is None:
+            adam_flat_(self.flat, self.grads, self.exp_avg, self.exp_avg_sq, 0, lr=self.lr, guard=self.guard,
+                       step_dev=self.step_dev)
+            return
+        if self._clip_scratch is None:
+            raise RuntimeError("aaa: the loaded library has no aaa_grad_norm (an older build under AAA_LIB); "
+                               "max_grad_norm needs it -- there is no fallback")
+        N.grad_norm(self.max_grad_norm, [self.grads], self.grad_stats, self._clip_scratch,
+                    stream=N.stream_ptr(self.device))
         adam_flat_(self.flat, self.grads, self.exp_avg, self.exp_avg_sq, 0, lr=self.lr, guard=self.guard,
-                   step_dev=self.step_dev)
+                   step_dev=self.step_dev, clip=self.grad_stats)
+
+    def clip_report(self) -> dict:
+        """The last clipped step's norm, coefficient, non-finite flag and
+        max_norm (reads the device: syncs; for logging, outside the iteration)."""
+        norm, coef, bad, mx = self.grad_stats.tolist()
+        return {"norm": norm, "coef": coef, "nonfinite": int(bad), "max_norm": mx}
 
     def train_step(self, frames, dlogits, dvalues, overlap: bool = True, reset=None):
         out = self.step(frames, dlogits, dvalues, overlap=overlap, reset=reset)

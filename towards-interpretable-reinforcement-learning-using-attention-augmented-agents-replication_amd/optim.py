@@ -19,7 +19,7 @@ from torch.autograd.graph import increment_version
 
 from . import _native as N
 
-__all__ = ["Adam", "adam_flat_"]
+__all__ = ["Adam", "adam_flat_", "clip_grad_norm_"]
 
 
 class Adam(torch.optim.Optimizer):
@@ -100,12 +100,59 @@ def _bump_versions(ps) -> None:
 
 def adam_flat_(params: torch.Tensor, grads: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor,
                step: int, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-               guard: torch.Tensor | None = None, step_dev: torch.Tensor | None = None) -> None:
+               guard: torch.Tensor | None = None, step_dev: torch.Tensor | None = None,
+               clip: torch.Tensor | None = None) -> None:
     """Adam over one flat fp32 buffer (the Learner's state_dict-ordered params): one launch.
     ``guard`` (one fp32 device element): skip the update on the device when it is non-zero.
     ``step_dev`` (one int32 device element, updates applied so far): use it instead of
-    ``step`` and advance it on the device only when the update ran."""
+    ``step`` and advance it on the device only when the update ran.
+    ``clip`` (the 4-element stats ``_native.grad_norm`` wrote; needs ``step_dev``): the update
+    runs on ``grads * clip[1]`` and is skipped, like a guarded one, when ``clip[2] != 0``."""
     hp = N.AdamHP(float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), 0, 0)
     N.adam_step(hp, step, [params], [grads], [exp_avg], [exp_avg_sq], None, stream=N.stream_ptr(params.device),
-                guard=guard, step_dev=step_dev)
+                guard=guard, step_dev=step_dev, clip=clip)
     _bump_versions([params])
+
+
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None, *,
+                    stats: torch.Tensor | None = None) -> torch.Tensor:
+    """``torch.nn.utils.clip_grad_norm_`` on the device (include/aaa.h ``aaa_grad_norm`` +
+    ``aaa_grad_scale``): the total 2-norm of the parameters' gradients, summed in
+    double in a fixed order, and the in-place scale by min(1, max_norm / (norm +
+    1e-6)) -- over any number of contiguous fp32 device gradients, with no host
+    sync.  Returns the 0-d device norm (element 0 of the stats; pass ``stats``, 4
+    fp32 device elements, to keep [norm, coefficient, non-finite flag, max_norm]).
+    ``error_if_nonfinite=True`` reads the flag, which syncs.  ``foreach`` is
+    accepted and ignored.  There is no CPU fallback.
+
+    ``stats=`` is an extension of torch's signature (keyword-only, so positional
+    callers are unaffected): torch returns only the norm, and the coefficient and
+    the flag would otherwise need a host read to recompute.  The scratch of the
+    partial sums is allocated per call; torch's caching allocator hands a freed
+    block to later work on the same stream only, so releasing it on return while
+    the kernels are still queued is safe."""
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    if float(norm_type) != 2.0:
+        raise ValueError(f"aaa_amd.optim.clip_grad_norm_: only norm_type=2 is supported (got {norm_type})")
+    grads = [p.grad for p in parameters if p.grad is not None]
+    if not grads:
+        return torch.tensor(0.0)
+    for g in grads:
+        if not g.is_cuda or g.dtype != torch.float32 or not g.is_contiguous():
+            raise RuntimeError("aaa_amd.optim.clip_grad_norm_: gradients must be contiguous fp32 tensors on the "
+                               "gfx950 device (there is no CPU fallback)")
+    dev = grads[0].device
+    if stats is None:
+        stats = torch.empty(4, device=dev)
+    scratch = torch.empty(N.grad_norm_scratch_bytes([g.numel() for g in grads]) // 8, dtype=torch.float64, device=dev)
+    st = N.stream_ptr(dev)
+    N.grad_norm(float(max_norm), grads, stats, scratch, stream=st)
+    if error_if_nonfinite and float(stats[2].item()) != 0.0:   # as torch: raised before any gradient is scaled
+        raise RuntimeError(f"The total norm of order {float(norm_type)} for gradients from `parameters` is "
+                           "non-finite, so it cannot be clipped. To disable this error and scale the gradients "
+                           "by the non-finite norm anyway, set `error_if_nonfinite=False`")
+    N.grad_scale(stats, grads, stream=st)
+    for g in grads:
+        increment_version(g)
+    return stats[0]
