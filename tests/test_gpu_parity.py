@@ -145,11 +145,9 @@ def test_unroll_vs_oracle_fp32(cuda, T, B):
     _compare(_run_unroll(_agent(cuda), T, B, cuda), _oracle(T, B), RTOL)
 
 
-# Every per-step tile variant of the ConvLSTM forward / BPTT GEMMs (runtime.hip
-# step_tile: 0 64x64, 1/2 split-K, 3 BK=128 split-K, 4-6 the LDS-DMA ring of
-# glds.h, 9 the 64x32 BPTT ring, 10-18 the 32x32 / 64x32 / 64x64 ring variants, 27-29 the fp32
-# split-product BPTT rings -- bf16 maps them to 4) must give the same answer;
-# B=5 makes B*P = 605 pixels (ragged tiles).
+# Every per-step tile variant of the ConvLSTM forward / BPTT GEMMs (the ids:
+# csrc/step_tiles.h; an id of the other family or the other operand type runs
+# tile 4) must give the same answer; B=5 makes B*P = 605 pixels (ragged tiles).
 @pytest.mark.parametrize("fwd,bwd", [(0, 0), (1, 1), (2, 2), (3, 3), (4, 4), (5, 5), (6, 6), (7, 4), (7, 7), (4, 8), (4, 9),
                                      (6, 10), (6, 11), (12, 12), (14, 13), (17, 15), (18, 16),
                                      (4, 19), (4, 20), (4, 21), (4, 22), (4, 23), (4, 24), (25, 16), (26, 16),
@@ -181,9 +179,7 @@ def test_fused_x_part_both_ways(cuda, monkeypatch, fused, conv_dtype):
         _bf16_checked(cuda, T, B, f"bf16 fused_x={fused}: ")
 
 
-# Every tile of the fused [x | h] forward step (runtime.hip AAA_FUSED_TILE: 4 128x64 8 waves,
-# 7 64x64, 8/10 3-stage rings, 9 128x128 4 waves (bf16 default), 11 2-way split-K, 12 128x64 4 waves,
-# 13-16 the fp32 split-product tiles, 17/18 their split-K forms (K-slice partials + gate_fwd_zx)).
+# Every tile of the fused [x | h] forward step (AAA_FUSED_TILE; the ids: csrc/step_tiles.h).
 @pytest.mark.parametrize("tile", ["4", "7", "8", "9", "10", "11", "12", "13", "14", "15", "16", "17", "18"])
 @pytest.mark.parametrize("conv_dtype", ["fp32", "bf16"])
 def test_fused_step_tiles(cuda, monkeypatch, tile, conv_dtype):
@@ -261,6 +257,20 @@ def test_fused_split_tiles_refuse_bf16(cuda, monkeypatch):
     monkeypatch.setenv("AAA_FUSED_TILE", "13")
     with pytest.raises(RuntimeError, match="split-product"):
         _run_unroll(_agent(cuda, conv_dtype="bf16"), 2, 2, cuda)
+
+
+def test_unknown_tile_ids_refused(cuda, monkeypatch):
+    """An id that no table of csrc/step_tiles.h holds is refused, in a message that
+    names the variable (it used to run the default tile, the BPTT with another
+    tile's gate-bias partials); the refusals leave the process usable."""
+    monkeypatch.setenv("AAA_FRAMES_FWD", "0")
+    T, B = 1, 2
+    for var in ("AAA_BPTT_TILE", "AAA_STEP_TILE"):
+        with monkeypatch.context() as m:
+            m.setenv(var, "40")
+            with pytest.raises(RuntimeError, match=var):
+                _run_unroll(_agent(cuda), T, B, cuda)
+    _compare(_run_unroll(_agent(cuda), T, B, cuda), _oracle(T, B), RTOL, "after the refusals: ")
 
 
 # The frame-resident bf16 recurrence (csrc/recur.h: one workgroup per frame for

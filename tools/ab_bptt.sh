@@ -1,5 +1,5 @@
 #!/bin/bash
-# Parity of the step tile variants, then A/Bs of AAA_STEP_TILE / AAA_BPTT_TILE on the given config.
+# Parity of the step tile variants, then A/Bs of AAA_STEP_TILE / AAA_BPTT_TILE (the ids: csrc/step_tiles.h) on the given config.
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out; mkdir -p $O; cd $R
 timeout -k 10 300 python -u -m pytest tests/test_gpu_parity.py -q -m gpu -x -p no:cacheprovider --timeout 120 --timeout-method thread -k "tile_variants" > $O/parity.log 2>&1 || { echo "tests rc=$?"; tail -30 $O/parity.log; exit 1; }
 tail -1 $O/parity.log

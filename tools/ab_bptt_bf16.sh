@@ -1,5 +1,5 @@
 #!/bin/bash
-# Parity of the step tile variants, then an A/B of the bf16 BPTT tile (AAA_BPTT_TILE 7, 8, 19-24) on the given configs.
+# Parity of the step tile variants, then an A/B of the bf16 BPTT tile (AAA_BPTT_TILE 7, 8, 19-24; the ids: csrc/step_tiles.h) on the given configs.
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out; mkdir -p $O; cd $R
 timeout -k 10 300 python -u -m pytest tests/test_gpu_parity.py -q -m gpu -x -p no:cacheprovider --timeout 120 --timeout-method thread -k "tile_variants" > $O/parity.log 2>&1 || { echo "tests rc=$?"; tail -30 $O/parity.log; exit 1; }
 tail -1 $O/parity.log

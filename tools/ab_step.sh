@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B the per-step tile choices: tools/ab_step.sh "FWD:BWD" ... (runtime.hip step_tile ids).
+# A/B the per-step tile choices: tools/ab_step.sh "FWD:BWD" ... (the ids: csrc/step_tiles.h).
 # Runs the tile-variant parity tests first; stops at the first failure.
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out; mkdir -p $O; cd $R
 timeout -k 10 600 python -m pytest tests/test_gpu_parity.py -q -x -p no:cacheprovider -k "tile_variants" > $O/parity.log 2>&1; rc=$?; echo "parity rc=$rc"; tail -3 $O/parity.log; [ $rc -eq 0 ] || exit $rc

@@ -1,8 +1,9 @@
 // Internal header of the host runtime (csrc/runtime.hip and the rt_*.hip
 // translation units): the buffer layout, error/timing/stream state (defined
-// once in rt_core.hip), the tile configurations and the GEMM launch helpers
-// shared by the forward (rt_forward.hip), the backward (rt_backward.hip) and
-// the component entries (rt_components.hip).
+// once in rt_core.hip) and the GEMM launch helpers shared by the forward
+// (rt_forward.hip), the backward (rt_backward.hip) and the component entries
+// (rt_components.hip).  The tile configurations and the per-step kernels'
+// tile ids: step_tiles.h.
 #pragma once
 #include <algorithm>
 #include <cstdarg>
@@ -34,6 +35,7 @@
 #include "misc.h"
 #include "optim.h"
 #include "actor.h"
+#include "step_tiles.h"
 
 
 namespace aaa {
@@ -184,42 +186,9 @@ inline double attn_bwd_bytes(int P, int nq, int oesz = 4) {
   return oesz * 128.0 * P + 4.0 * (128.0 * P + nq * P + 184.0 * nq + 72.0 * nq);
 }
 
-// --------------------------------------------------------- tile configs ---
-// fp32 uses the exact v_mfma_f32_32x32x2_f32; bf16 v_mfma_f32_32x32x16_bf16 (fp32 accumulate).
-using CF = GemmCfg<float, 64, 64, 32, 2, 2>;      // default 64x64 tile, 4 waves
-using CF32 = GemmCfg<float, 32, 64, 32, 1, 2>;    // 32-row tile, 2 waves: small-Mi GEMMs / more WGs
-using CFW = GemmCfg<float, 128, 128, 32, 2, 2>;   // long-K weight gradients: 64x64 per wave
-using CFK = GemmCfg<float, 32, 64, 64, 1, 2, 2>;  // per-step ConvLSTM kernels: 2-way split-K in the WG
-using CFK4 = GemmCfg<float, 32, 64, 64, 1, 2, 4>; // 4-way split-K (8 waves)
-using CFK4B = GemmCfg<float, 32, 64, 128, 1, 2, 4>; // 4-way split-K, 2 k-steps per wave per barrier
-using CF64 = GemmCfg<float, 64, 64, 64, 2, 2>;     // 64x64, BK 64
-using CFJ = GemmCfg<float, 64, 128, 32, 2, 2>;     // 64-row GEMMs with long N (batched dx)
-using CFS = GemmCfg<float, 128, 64, 32, 4, 2>;     // forward step: 8 waves, ~1 WG per CU at C2 (balanced)
-using CB = GemmCfg<__bf16, 64, 64, 64, 2, 2>;
-using CB32 = GemmCfg<__bf16, 32, 64, 64, 1, 2>;
-using CBW = GemmCfg<__bf16, 128, 128, 64, 2, 2>;
-using CBK = GemmCfg<__bf16, 32, 64, 64, 1, 2, 2>;
-using CBK4 = GemmCfg<__bf16, 32, 64, 64, 1, 2, 4>;
-using CBK4B = GemmCfg<__bf16, 32, 64, 128, 1, 2, 4>;
-using CB64 = GemmCfg<__bf16, 64, 64, 128, 2, 2>;
-using CBJ = GemmCfg<__bf16, 64, 128, 64, 2, 2>;
-using CBS = GemmCfg<__bf16, 128, 64, 64, 4, 2>;
-template <typename T> using CfgFor = std::conditional_t<std::is_same<T, float>::value, CF, CB>;
-template <typename T> using Cfg32For = std::conditional_t<std::is_same<T, float>::value, CF32, CB32>;
-template <typename T> using CfgWFor = std::conditional_t<std::is_same<T, float>::value, CFW, CBW>;
-template <typename T> using CfgKFor = std::conditional_t<std::is_same<T, float>::value, CFK, CBK>;
-template <typename T> using CfgK4For = std::conditional_t<std::is_same<T, float>::value, CFK4, CBK4>;
-template <typename T> using CfgK4BFor = std::conditional_t<std::is_same<T, float>::value, CFK4B, CBK4B>;
-template <typename T> using Cfg64For = std::conditional_t<std::is_same<T, float>::value, CF64, CB64>;
-template <typename T> using CfgJFor = std::conditional_t<std::is_same<T, float>::value, CFJ, CBJ>;
-template <typename T> using CfgSFor = std::conditional_t<std::is_same<T, float>::value, CFS, CBS>;
-
-// Step-kernel tile choice (env AAA_STEP_TILE / AAA_BPTT_TILE override):
-//   0 64x64 BK32 | 1 32x64 BK64 2-way in-WG split-K | 2 ... 4-way | 3 32x64 BK128 4-way
-//   (forward: 3 = 64x64 BK64) | 4-6 the same shapes on the LDS-DMA ring of glds.h
-//   (forward 4 = 128x64 8 waves, 5 = 32x64 split-K, 6 = 64x64 BK64; BPTT 4 = 32x64 BK128
-//   4-way, 5 = BK64 4-way, 6 = 64x64, 9 = 64x32 BK128 4-way).  The default picks by how many 32x32
-//   output tiles the step has, i.e. how many waves it can feed; measured on C2.
+// Step-kernel tile choice (env AAA_STEP_TILE / AAA_BPTT_TILE override; the ids:
+// step_tiles.h).  The default picks by how many 32x32 output tiles the step has,
+// i.e. how many waves it can feed; measured on C2.
 // (env_int: common.h)
 // A/B-only knobs (the same-box comparisons of tools/gpu_ab*.sh): read from the
 // environment only in -DAAA_ABLATION builds (make ablation -> libaaa_ablation.so,
@@ -240,15 +209,14 @@ static int chunk_steps(const Layout& L) {
   return std::max(1, std::min({c, L.T, L.fchunk / L.B}));
 }
 bool f32_split6();   // fp32 path: large GEMMs as bf16x6 split products (rt_core.hip)
+// An id of another family, or one this family holds for the other operand type only, runs tile 4
+// (every family has a 4).  < 0: the variable names an id that no family holds; the caller
+// refuses (tile_unknown).
 static int step_tile(long out_tiles32, const char* env, bool bptt, bool bf16 = false) {
   const int v = env_int(env, -1);
-  if (v >= 0) {   // 7, 8: bf16 only; 9-11, 13, 15, 16: BPTT only; 14, 17, 18: forward only
-    const bool bptt_only = v == 9 || v == 10 || v == 11 || v == 13 || v == 15 || v == 16 || (v >= 19 && v <= 24) ||
-                           (v >= 27 && v <= 33);
-    if (v >= 19 && v <= 24 && !bf16) return 4;   // 19-24: bf16 BPTT tiles (fp16 gate storage)
-    if (v >= 27 && v <= 33 && bf16) return 4;    // 27-33: fp32 split-product BPTT tiles (30-33 split-K)
-    const bool fwd_only = v == 14 || v == 17 || v == 18 || v == 25 || v == 26;
-    return ((v == 7 || v == 8) && !bf16) || (bptt_only && !bptt) || (fwd_only && bptt) ? 4 : v;
+  if (v >= 0) {
+    const unsigned served = bptt ? tile_dt(BpttTiles{}, v) : tile_dt(FwdTiles{}, v);
+    return served & (bf16 ? kBf16 : kF32) ? v : (tile_known(v) ? 4 : -1);
   }
   // bf16 BPTT: 128x128 from ~3/4 of a workgroup per CU (C3: 242 WGs), else 128x64
   // (tools/ubench/bf16_tiles at B=128: 34.6 vs 39.6 us)
@@ -264,6 +232,9 @@ static int step_tile(long out_tiles32, const char* env, bool bptt, bool bf16 = f
   // episode's 27x20 grid; C2 itself runs the frame-group BPTT, recur_bwd_f32.h)
   if (bptt) return out_tiles32 < 1024 ? (f32_split6() ? 31 : 16) : (out_tiles32 < 1536 ? 1 : 0);
   return out_tiles32 < 1024 ? 5 : 6;
+}
+static int tile_unknown(const char* env) {
+  return fail(AAA_E_ARG, "%s %d: no such tile id (csrc/step_tiles.h)", env, env_int(env, -1));
 }
 
 // Split-K BPTT (fp32 tiles 30/31): K slices of the per-step dh dgrad, summed by
@@ -281,7 +252,7 @@ inline int splitk_slices(int K, int BK, int nsplit) {
 
 // fp16 gate-activation storage (halves the step epilogues' largest stream):
 // bf16 operands, fused x-part (the gate buffer then holds activations only)
-// and the bf16 BPTT tiles 7/8.  AAA_GATES_F16=0 keeps fp32.  Forward and
+// and a bf16 BPTT tile that reads them (step_tiles.h kG16).  AAA_GATES_F16=0 keeps fp32.  Forward and
 // backward evaluate this identically (same env, same shapes).
 // The x-part rides in the step GEMM for bf16 and for small steps (M = B*P
 // pixels; the actor's B = 1: one launch instead of two latency-bound ones);
@@ -296,14 +267,7 @@ static bool fused_x(int dt, int M) { return env_int("AAA_FUSED_X", dt == AAA_BF1
 static bool gates_f16(int dt, int M) {
   if (dt != AAA_BF16 || !fused_x(dt, M) || !ab_int("AAA_GATES_F16", 1)) return false;
   const int bt = step_tile((long)(128 / 32) * ((M + 31) / 32), "AAA_BPTT_TILE", true, true);
-  return bt == 7 || bt == 8 || bt >= 19;
-}
-
-// Whether the LDS-DMA ring can run tile config CK (every wave issues the same DMA count).
-template <class CK>
-constexpr bool pipe_even() {
-  constexpr int VG = 16 / (int)sizeof(typename CK::type);
-  return (CK::BI * CK::BK / VG) % CK::NT == 0 && (CK::BJ * CK::BK / VG) % CK::NT == 0;
+  return (tile_gates(BpttTiles{}, bt) & kG16) != 0;
 }
 
 // One per-step ConvLSTM GEMM: D[Mi][M] = W[Mi][K] x im2col(src)[K][M] with
@@ -539,57 +503,34 @@ static int fused_step(const T* WpXH, const T* xht, int h, int w, int M, const Ep
   // (B=1 episode step, 27x20 grid: 16.2 + 5.0 us vs 68 us for the fp32 128x64
   // tile, 23 us for 13 = 32x64 4-way in-WG; tools/gpu_episode_ab.sh), 13 where
   // there is no split-K scratch
-  const int ftile = env_int("AAA_FUSED_TILE", f32 ? (f32_split6() ? (zpart ? 18 : 13) : 4) : 9);
-  TimerScope tim(AAA_TIMER_FWD_STEP, st, 2.0 * M * 512 * 1728,
-                 strf("%s fused [x|h] step, K=1728, AAA_FUSED_TILE %d%s [kernel: EpiConvLstmFwd]%s", f32 ? "fp32" : "bf16",
-                      ftile, f32 && ftile >= 13 && ftile <= 16 ? " (bf16x6 split products)" : "",
-                      resets ? ", resets" : ""));
-  if (ftile == 17 || ftile == 18) {   // split-K (bf16x6 split products)
-    if constexpr (!f32 || !std::is_same<GT, float>::value) {
+  const int want = env_int("AAA_FUSED_TILE", f32 ? (f32_split6() ? (zpart ? 18 : 13) : 4) : 9);
+  // as step_tile: another family's id runs tile 4, an id of no family is refused
+  const int ftile = tile_dt(FusedTiles{}, want) ? want : 4;
+  if (ftile != want && !tile_known(want)) return tile_unknown("AAA_FUSED_TILE");
+  return for_tile<FusedTiles>(ftile, (int)AAA_E_ARG, [&](auto tile) -> int {
+    using Tl = decltype(tile);
+    using CK = typename Tl::template Cfg<T>;
+    constexpr bool slices = Tl::split == SplitK::Slices;
+    TimerScope tim(AAA_TIMER_FWD_STEP, st, 2.0 * M * 512 * 1728,
+                   strf("%s fused [x|h] step, K=1728, AAA_FUSED_TILE %d%s [kernel: EpiConvLstmFwd]%s", f32 ? "fp32" : "bf16",
+                        ftile, f32 && Tl::split_product && !slices ? " (bf16x6 split products)" : "",
+                        resets ? ", resets" : ""));
+    if constexpr (!Tl::template serves<T, GT>()) {
       return fail(AAA_E_ARG, "AAA_FUSED_TILE %d: fp32 split-product tiles only", ftile);
-    } else {
+    } else if constexpr (slices) {   // K-slice partials of the gate pre-activations, then the cell
       if (!zpart || !ep.bias) return fail(AAA_E_ARG, "AAA_FUSED_TILE %d: split-K needs B*P < 8192 (got %d)", ftile, M);
-      const int ns = splitk_slices(1728, 64, fused_splitk());
+      const int ns = splitk_slices(1728, CK::BK, fused_splitk());
       const EpiSliceT es{zpart, 512, 512, M, (size_t)M * 512};
-      if (ftile == 17)
-        HIPCHK((step_gemm_splitk<GemmCfgS6<32, 64, 64, 1, 2, 4>>(WpXH, 1728, 512, xht, g, M, xh_bytes, es, 512, 1728,
-                                                                 st, ns)));
-      else
-        HIPCHK((step_gemm_splitk<GemmCfgS6<64, 64, 64, 2, 2, 2>>(WpXH, 1728, 512, xht, g, M, xh_bytes, es, 512, 1728,
-                                                                 st, ns)));
-      HIPCHK(gate_fwd_zx<T>(M, ep.cprev, ep.gates, ep.cnext, ep.hout, ep.xhnext, st, zpart, ns, (size_t)M * 512,
-                            ep.bias));
-      return AAA_OK;
+      HIPCHK((step_gemm_splitk<CK>(WpXH, 1728, 512, xht, g, M, xh_bytes, es, 512, 1728, st, ns, Tl::ILV)));
+      // (CK::type is T; spelled through the entry so that the call is only checked where the entry serves GT)
+      HIPCHK(gate_fwd_zx<typename CK::type>(M, ep.cprev, ep.gates, ep.cnext, ep.hout, ep.xhnext, st, zpart, ns,
+                                            (size_t)M * 512, ep.bias));
+    } else {
+      HIPCHK((step_gemm<CK, Tl::stage != Stage::Reg, T, T, EF, Tl::NBUF, Tl::ILV>(WpXH, 1728, 512, xht, g, M, xh_bytes, ep, 512,
+                                                                                  1728, st)));
     }
-  }
-  if (ftile >= 13 && ftile <= 16) {
-    if constexpr (!f32) return fail(AAA_E_ARG, "AAA_FUSED_TILE %d: fp32 split-product tiles only", ftile);
-    else if (ftile == 13)
-      HIPCHK((step_gemm<GemmCfgS6<32, 64, 64, 1, 2, 4>, true>(WpXH, 1728, 512, xht, g, M, xh_bytes, ep, 512, 1728, st)));
-    else if (ftile == 14)
-      HIPCHK((step_gemm<GemmCfgS6<64, 64, 64, 2, 2, 2>, true>(WpXH, 1728, 512, xht, g, M, xh_bytes, ep, 512, 1728, st)));
-    else if (ftile == 15)
-      HIPCHK((step_gemm<GemmCfgS6<128, 64, 32, 4, 2>, true>(WpXH, 1728, 512, xht, g, M, xh_bytes, ep, 512, 1728, st)));
-    else
-      HIPCHK((step_gemm<GemmCfgS6<32, 32, 64, 1, 1, 4>, true, T, T, EF, 3>(WpXH, 1728, 512, xht, g, M, xh_bytes, ep,
-                                                                             512, 1728, st)));
     return AAA_OK;
-  }
-  if (ftile == 7)
-    HIPCHK((step_gemm<CfgFor<T>, true>(WpXH, 1728, 512, xht, g, M, xh_bytes, ep, 512, 1728, st)));
-  else if (ftile == 8)   // 128x64, 8 waves, 3-stage ring
-    HIPCHK((step_gemm<CfgSFor<T>, true, T, T, EF, 3, true>(WpXH, 1728, 512, xht, g, M, xh_bytes, ep, 512, 1728, st)));
-  else if (ftile == 9)   // 128x128, 4 waves of 64x64
-    HIPCHK((step_gemm<GemmCfg<T, 128, 128, 64, 2, 2>, true>(WpXH, 1728, 512, xht, g, M, xh_bytes, ep, 512, 1728, st)));
-  else if (ftile == 10)   // 64x64, 4 waves, 3-stage ring
-    HIPCHK((step_gemm<CfgFor<T>, true, T, T, EF, 3, true>(WpXH, 1728, 512, xht, g, M, xh_bytes, ep, 512, 1728, st)));
-  else if (ftile == 11)   // 64x64, 2-way in-WG split-K (8 waves), BK64 (K = 1728 = 27 x 64)
-    HIPCHK((step_gemm<GemmCfg<T, 64, 64, 64, 2, 2, 2>, true>(WpXH, 1728, 512, xht, g, M, xh_bytes, ep, 512, 1728, st)));
-  else if (ftile == 12)   // 128x64, 2x2 waves of 64x32
-    HIPCHK((step_gemm<GemmCfg<T, 128, 64, 64, 2, 2>, true>(WpXH, 1728, 512, xht, g, M, xh_bytes, ep, 512, 1728, st)));
-  else
-    HIPCHK((step_gemm<CfgSFor<T>, true>(WpXH, 1728, 512, xht, g, M, xh_bytes, ep, 512, 1728, st)));
-  return AAA_OK;
+  });
 }
 
 // ---------------------------------------------- frame-resident dispatch ----

@@ -642,7 +642,6 @@ static int head_backward_stateful(const Layout& L, const aaa_io* io, hipStream_t
 
 template <typename T>
 int backward_impl(const Layout& L, const aaa_io* io, int phases, hipStream_t st, const float* reset) {
-  using C = CfgFor<T>;
   // bf16 path: the fp32 tail GEMMs on the bf16 MFMA with split operands (AAA_TAIL_SPLIT3=0: fp32 MFMA)
   TailPrecision tail_prec(std::is_same<T, __bf16>::value && env_int("AAA_TAIL_SPLIT3", 1),
                           std::is_same<T, float>::value && f32_split6());
@@ -926,20 +925,20 @@ int backward_impl(const Layout& L, const aaa_io* io, int phases, hipStream_t st,
     // Sequential part: only the h rows (dh_{t-1}, fused with the gate backward
     // of step t-1); everything else runs in chunks off the chain.
     const int bwd_tile = step_tile((long)(128 / 32) * cdiv(M, 32), "AAA_BPTT_TILE", true, L.dt == AAA_BF16);
-    // pipe (glds.h) tiles reduce the gate-bias partials in their epilogue;
-    // the register-staged ones leave the bias to a column sum over dZ
-    // (split-K tiles 30/31: the gate backward kernel's pixel tile, kSplitBj -- finer than the GEMM's, so
-    // that kernel spreads over the chip)
-    const int bj = bwd_tile >= 30 && bwd_tile <= 33 ? kSplitBj : (bwd_tile == 7 || bwd_tile == 19 || bwd_tile == 20 ? 128 : (bwd_tile == 21 || bwd_tile == 22 || bwd_tile == 23 ? 64 : (bwd_tile >= 9 && bwd_tile != 14 ? 32 : 64)));
-    const bool pipe = (bwd_tile == 4 && pipe_even<CfgK4BFor<T>>()) || (bwd_tile == 5 && pipe_even<CfgK4For<T>>()) ||
-                      (bwd_tile == 6 && pipe_even<C>()) || bwd_tile == 7 || bwd_tile == 8 || bwd_tile >= 19 ||
-                      (bwd_tile == 9 && pipe_even<GemmCfg<T, 64, 32, 128, 2, 1, 4>>()) ||
-                      (bwd_tile == 10 && pipe_even<GemmCfg<T, 32, 32, 128, 1, 1, 4>>()) ||
-                      ((bwd_tile == 11 || bwd_tile == 12 || bwd_tile == 16) && pipe_even<GemmCfg<T, 32, 32, 64, 1, 1, 4>>()) ||
-                      (bwd_tile == 13 && pipe_even<GemmCfg<T, 32, 32, 128, 1, 1, 8>>()) ||
-                      (bwd_tile == 15 && pipe_even<GemmCfg<T, 64, 32, 64, 2, 1, 4>>()) ||
-                      (bwd_tile >= 27 && bwd_tile <= 31);   // fp32 split-product tiles (ring only)
-    const bool fixk = bwd_tile == 32 || bwd_tile == 33;   // split-K finished in the GEMM: bias from dZ's column sum
+    if (bwd_tile < 0) return tile_unknown("AAA_BPTT_TILE");
+    // From the tile's entry (step_tiles.h).  bj: the pixels per gate-backward workgroup and gate-bias partial
+    // row -- the GEMM's pixel tile (split-K chain: kSplitBj, finer, so that kernel spreads over the chip).
+    // pipe: ring (glds.h) kernels reduce the gate-bias partials in their epilogue; the register-staged
+    // ones leave the bias to a column sum over dZ.  dh0: the entry that runs t = 0 (dh0).
+    struct Chain { int bj; bool pipe; SplitK split; int dh0; };
+    const Chain chain = for_tile<BpttTiles>(bwd_tile, Chain{}, [](auto tile) {
+      using Tl = decltype(tile);
+      return Chain{Tl::split == SplitK::None ? Tl::template Cfg<T>::BJ : kSplitBj, Tl::template pipe<T>(), Tl::split,
+                   Tl::dh0};
+    });
+    const int bj = chain.bj;
+    const bool pipe = chain.pipe;
+    const bool fixk = chain.split == SplitK::SliceFix;   // split-K finished in the GEMM: bias from dZ's column sum
     if (fixk && L.dhs)   // the fixup counters (self-resetting; zeroed per call in case a launch was abandoned)
       HIPCHK(hipMemsetAsync(ws + L.dhs + (size_t)std::max(kBpttSplitMax * 128, 4 * 512) * M * 4, 0, 4096, st));
     const int ntj = cdiv(M, bj);
@@ -1074,161 +1073,50 @@ int backward_impl(const Layout& L, const aaa_io* io, int phases, hipStream_t st,
       const ConvGeo g = ConvGeo{512, 512, 0, L.h, L.w, L.h, L.w, 3, 1, 1, 1}.prep();
       const T* dzt = Wt(L.dZ) + (size_t)t * M * 512;
       TimerScope tim(AAA_TIMER_BPTT_STEP, st, 2.0 * M * 128 * 4608, strf("%s dh dgrad + fused gate bwd, K=4608, AAA_BPTT_TILE %d%s%s", std::is_same<T, float>::value ? "fp32" : "bf16", bwd_tile, g16 ? ", fp16 gates [kernel: EpiConvLstmBwd]" : " [kernel: EpiConvLstmBwd]", reset ? ", resets" : ""));
-      if constexpr (std::is_same<T, float>::value) {
-        if (fixk && prev) {   // split-K, the last slice of each tile runs the gate backward (EpiSliceFix)
-          if (!L.dhs) return fail(AAA_E_ARG, "AAA_BPTT_TILE %d: split-K needs B*P < 8192 (got %d)", bwd_tile, M);
-          const int bk = bwd_tile == 32 ? 64 : 128;
-          const int ns = splitk_slices(4608, bk, bptt_splitk());
-          float* dhp = Wf(L.dhs);
-          int* cnt = (int*)(ws + L.dhs + (size_t)std::max(kBpttSplitMax * 128, 4 * 512) * M * 4);
-          using EB = EpiConvLstmBwd<T, float>;
-          const EB eb{nullptr, (const float*)(ws + L.Gt) + (size_t)(t - 1) * M * 512, Wf(L.Cst) + (size_t)(t - 1) * M * 128,
-                      Wf(L.Cst) + (size_t)t * M * 128, Wf(L.dO) + (size_t)(t - 1) * M * 128, Wf(L.dC),
-                      Wt(L.dZ) + (size_t)(t - 1) * M * 512, nullptr, 1, M, 64, nullptr};
-          const EpiSliceFix<EB> ef{dhp, 128, 128, M, (size_t)M * 128, ns, cdiv(M, 32), cnt, eb};
-          if (bwd_tile == 32)
-            HIPCHK((step_gemm_splitk<GemmCfgS6<32, 32, 64, 1, 1, 4>>(WdTh, 4608, 128, dzt, g, M, dz_bytes, ef, 128,
-                                                                     4608, st, ns)));
-          else
-            HIPCHK((step_gemm_splitk<GemmCfgS6<32, 32, 128, 1, 1, 8>>(WdTh, 4608, 128, dzt, g, M, dz_bytes, ef, 128,
-                                                                      4608, st, ns, true)));
-          if (const int rc = fix(t)) return rc;
-          continue;
-        }
-        if ((bwd_tile == 30 || bwd_tile == 31) && prev) {   // split-K: K-slice partials, then the gate backward
-          if (!L.dhs) return fail(AAA_E_ARG, "AAA_BPTT_TILE %d: split-K needs B*P < 8192 (got %d)", bwd_tile, M);
-          const int bk = bwd_tile == 30 ? 64 : 128;
-          const int ns = splitk_slices(4608, bk, bptt_splitk());   // as launch_pipe rounds it
-          float* dhp = Wf(L.dhs);
-          const EpiSliceT es{dhp, 128, 128, M, (size_t)M * 128};
-          if (bwd_tile == 30)   // tile 27's shape
-            HIPCHK((step_gemm_splitk<GemmCfgS6<32, 32, 64, 1, 1, 4>>(WdTh, 4608, 128, dzt, g, M, dz_bytes, es, 128,
-                                                                     4608, st, ns)));
-          else                  // tile 28's shape (interleaved DMA)
-            HIPCHK((step_gemm_splitk<GemmCfgS6<32, 32, 128, 1, 1, 8>>(WdTh, 4608, 128, dzt, g, M, dz_bytes, es, 128,
-                                                                      4608, st, ns, true)));
-          HIPCHK((gate_bwd_last<T, float>(M, bj, Wf(L.dO) + (size_t)(t - 1) * M * 128, dhp,
-                                          Wf(L.Gt) + (size_t)(t - 1) * M * 512, Wf(L.Cst) + (size_t)(t - 1) * M * 128,
-                                          Wf(L.Cst) + (size_t)t * M * 128, Wf(L.dC), Wt(L.dZ) + (size_t)(t - 1) * M * 512,
-                                          part ? part + (size_t)(t - 1) * ntj * 512 : nullptr, st, ns,
-                                          (size_t)M * 128)));
-          if (const int rc = fix(t)) return rc;
-          continue;
-        }
-      }
-      auto step = [&](auto gtag) -> hipError_t {
+      const int tile_id = prev ? bwd_tile : chain.dh0;
+      auto step = [&](auto gtag) -> int {
         using GT = decltype(gtag);
-        using EB = EpiConvLstmBwd<T, GT>;
-        EB ep{nullptr,
-              prev ? (const GT*)(ws + L.Gt) + (size_t)(t - 1) * M * 512 : nullptr,
-              prev ? Wf(L.Cst) + (size_t)(t - 1) * M * 128 : nullptr,
-              Wf(L.Cst) + (size_t)t * M * 128,
-              prev ? Wf(L.dO) + (size_t)(t - 1) * M * 128 : nullptr,
-              Wf(L.dC),
-              prev ? Wt(L.dZ) + (size_t)(t - 1) * M * 512 : nullptr,
-              prev ? nullptr : io->dh0, prev ? 1 : 0, M, 64,
-              part && prev ? part + (size_t)(t - 1) * ntj * 512 : nullptr};
-        if constexpr (!std::is_same<GT, float>::value) {   // fp16 gates: the bf16 tiles only (gates_f16)
-          if constexpr (std::is_same<T, float>::value) return hipErrorInvalidValue;
-          else if (bwd_tile == 7)
-            return step_gemm<GemmCfg<T, 128, 128, 128, 2, 2, 2>, true>(WdTh, 4608, 128, dzt, g, M, dz_bytes, ep, 128,
-                                                                        4608, st);
-          else if (bwd_tile == 19)   // 128x128, 4 waves of 64x64, BK64
-            return step_gemm<GemmCfg<T, 128, 128, 64, 2, 2>, true>(WdTh, 4608, 128, dzt, g, M, dz_bytes, ep, 128, 4608,
-                                                                    st);
-          else if (bwd_tile == 20)   // the same on a 3-stage ring
-            return step_gemm<GemmCfg<T, 128, 128, 64, 2, 2>, true, T, T, EB, 3, true>(WdTh, 4608, 128, dzt, g, M,
-                                                                                      dz_bytes, ep, 128, 4608, st);
-          else if (bwd_tile == 22)   // 128x64, BK128, 4-way in-WG split-K (8 waves)
-            return step_gemm<GemmCfg<T, 128, 64, 128, 2, 1, 4>, true>(WdTh, 4608, 128, dzt, g, M, dz_bytes, ep, 128,
-                                                                       4608, st);
-          else if (bwd_tile == 23)   // 64x64, BK128, 2-way in-WG split-K (8 waves)
-            return step_gemm<GemmCfg<T, 64, 64, 128, 2, 2, 2>, true>(WdTh, 4608, 128, dzt, g, M, dz_bytes, ep, 128,
-                                                                      4608, st);
-          else if (bwd_tile == 24)   // 64x32, BK128, 4-way in-WG split-K (8 waves)
-            return step_gemm<GemmCfg<T, 64, 32, 128, 2, 1, 4>, true>(WdTh, 4608, 128, dzt, g, M, dz_bytes, ep, 128,
-                                                                      4608, st);
-          else if (bwd_tile == 21)   // 128x64, 4 waves of 64x32, BK64
-            return step_gemm<GemmCfg<T, 128, 64, 64, 2, 2>, true>(WdTh, 4608, 128, dzt, g, M, dz_bytes, ep, 128, 4608,
-                                                                   st);
-          else
-            return step_gemm<GemmCfg<T, 128, 64, 128, 2, 1, 2>, true>(WdTh, 4608, 128, dzt, g, M, dz_bytes, ep, 128,
-                                                                       4608, st);
-        } else {
-          // tiles 19-24 other than 22 exist for fp16 gate storage only: fail loudly, never fall back
-          if (bwd_tile >= 19 && bwd_tile <= 24 && bwd_tile != 22) return hipErrorInvalidValue;
-          switch (bwd_tile) {
-            case 1: return step_gemm<CfgKFor<T>, false>(WdTh, 4608, 128, dzt, g, M, dz_bytes, ep, 128, 4608, st);
-            case 2: return step_gemm<CfgK4For<T>, false>(WdTh, 4608, 128, dzt, g, M, dz_bytes, ep, 128, 4608, st);
-            case 3: return step_gemm<CfgK4BFor<T>, false>(WdTh, 4608, 128, dzt, g, M, dz_bytes, ep, 128, 4608, st);
-            case 4:   // 3-stage ring, DMA interleaved with the MFMAs (tools/ubench/step_ablate: 57.9 vs 59.4 us)
-              return step_gemm<CfgK4BFor<T>, true, T, T, EB, 3, true>(WdTh, 4608, 128, dzt, g, M, dz_bytes, ep, 128,
-                                                                       4608, st);
-            case 5: return step_gemm<CfgK4For<T>, true>(WdTh, 4608, 128, dzt, g, M, dz_bytes, ep, 128, 4608, st);
-            case 6: return step_gemm<C, true>(WdTh, 4608, 128, dzt, g, M, dz_bytes, ep, 128, 4608, st);
-            case 7:   // bf16: 128x128, BK128, 2-way in-WG split-K (tools/ubench/bf16_tiles: 48 vs 53-60 us at C3)
-              if constexpr (std::is_same<T, float>::value) return hipErrorInvalidValue;
-              else return step_gemm<GemmCfg<T, 128, 128, 128, 2, 2, 2>, true>(WdTh, 4608, 128, dzt, g, M, dz_bytes, ep,
-                                                                              128, 4608, st);
-            case 8:   // bf16: 128x64, BK128, 2-way in-WG split-K, 4 waves (small batches)
-              if constexpr (std::is_same<T, float>::value) return hipErrorInvalidValue;
-              else return step_gemm<GemmCfg<T, 128, 64, 128, 2, 1, 2>, true>(WdTh, 4608, 128, dzt, g, M, dz_bytes, ep,
-                                                                             128, 4608, st);
-            case 22:   // bf16 with fp32 gate storage (AAA_FUSED_X=0 / AAA_GATES_F16=0): the default small-batch tile
-              if constexpr (std::is_same<T, float>::value) return hipErrorInvalidValue;
-              else return step_gemm<GemmCfg<T, 128, 64, 128, 2, 1, 4>, true>(WdTh, 4608, 128, dzt, g, M, dz_bytes, ep,
-                                                                             128, 4608, st);
-            case 9:   // 64x32, BK128, 4-way in-WG split-K, 3-stage ring, interleaved DMA
-              return step_gemm<GemmCfg<T, 64, 32, 128, 2, 1, 4>, true, T, T, EB, 3, true>(WdTh, 4608, 128, dzt, g, M,
-                                                                                          dz_bytes, ep, 128, 4608, st);
-            case 10:   // 32x32, BK128, 4-way in-WG split-K, 2-stage ring (2 WGs per CU, desynchronised barriers)
-              return step_gemm<GemmCfg<T, 32, 32, 128, 1, 1, 4>, true, T, T, EB, 2, true>(WdTh, 4608, 128, dzt, g, M,
-                                                                                         dz_bytes, ep, 128, 4608, st);
-            case 11:   // 32x32, BK64, 4-way in-WG split-K, 3-stage ring
-              return step_gemm<GemmCfg<T, 32, 32, 64, 1, 1, 4>, true, T, T, EB, 3, true>(WdTh, 4608, 128, dzt, g, M,
-                                                                                        dz_bytes, ep, 128, 4608, st);
-            case 12:   // 32x32, BK64, 4-way in-WG split-K, 4-stage ring
-              return step_gemm<GemmCfg<T, 32, 32, 64, 1, 1, 4>, true, T, T, EB, 4, true>(WdTh, 4608, 128, dzt, g, M,
-                                                                                        dz_bytes, ep, 128, 4608, st);
-            case 13:   // 32x32, BK128, 8-way in-WG split-K (8 waves), 2-stage ring
-              return step_gemm<GemmCfg<T, 32, 32, 128, 1, 1, 8>, true, T, T, EB, 2, true>(WdTh, 4608, 128, dzt, g, M,
-                                                                                         dz_bytes, ep, 128, 4608, st);
-            case 15:   // 64x32, BK64, 4-way in-WG split-K, 3-stage ring
-              return step_gemm<GemmCfg<T, 64, 32, 64, 2, 1, 4>, true, T, T, EB, 3, true>(WdTh, 4608, 128, dzt, g, M,
-                                                                                        dz_bytes, ep, 128, 4608, st);
-            case 16:   // 32x32, BK64, 4-way in-WG split-K, 3-stage ring, DMA issued before the MFMAs
-              return step_gemm<GemmCfg<T, 32, 32, 64, 1, 1, 4>, true, T, T, EB, 3, false>(WdTh, 4608, 128, dzt, g, M,
-                                                                                         dz_bytes, ep, 128, 4608, st);
-            // 27-29: fp32 as bf16x6 split products (gemm.h SPLIT6) on the small-batch shapes
-            case 27:   // tile 16's shape
-              if constexpr (!std::is_same<T, float>::value) return hipErrorInvalidValue;
-              else return step_gemm<GemmCfgS6<32, 32, 64, 1, 1, 4>, true, T, T, EB, 3, false>(WdTh, 4608, 128, dzt, g,
-                                                                                              M, dz_bytes, ep, 128,
-                                                                                              4608, st);
-            case 28:   // 32x32, BK128, 8-way in-WG split-K (8 waves), 2-stage ring
-              if constexpr (!std::is_same<T, float>::value) return hipErrorInvalidValue;
-              else return step_gemm<GemmCfgS6<32, 32, 128, 1, 1, 8>, true, T, T, EB, 2, true>(WdTh, 4608, 128, dzt, g,
-                                                                                              M, dz_bytes, ep, 128,
-                                                                                              4608, st);
-            case 30:   // split-K tiles: t = 0 (dh0) takes tile 27
-            case 31:
-            case 32:
-            case 33:
-              if constexpr (!std::is_same<T, float>::value) return hipErrorInvalidValue;
-              else return step_gemm<GemmCfgS6<32, 32, 64, 1, 1, 4>, true, T, T, EB, 3, false>(WdTh, 4608, 128, dzt, g,
-                                                                                              M, dz_bytes, ep, 128,
-                                                                                              4608, st);
-            case 29:   // 64x32, BK128, 4-way in-WG split-K, 3-stage ring
-              if constexpr (!std::is_same<T, float>::value) return hipErrorInvalidValue;
-              else return step_gemm<GemmCfgS6<64, 32, 128, 2, 1, 4>, true, T, T, EB, 3, true>(WdTh, 4608, 128, dzt, g,
-                                                                                              M, dz_bytes, ep, 128,
-                                                                                              4608, st);
-            default: return step_gemm<C, false>(WdTh, 4608, 128, dzt, g, M, dz_bytes, ep, 128, 4608, st);
+        using EB = EpiConvLstmBwd<T, GT>;   // the gate backward of step t-1 as the GEMM's epilogue (t = 0: dh0 out)
+        const EB ep{nullptr,
+                    prev ? (const GT*)(ws + L.Gt) + (size_t)(t - 1) * M * 512 : nullptr,
+                    prev ? Wf(L.Cst) + (size_t)(t - 1) * M * 128 : nullptr,
+                    Wf(L.Cst) + (size_t)t * M * 128,
+                    prev ? Wf(L.dO) + (size_t)(t - 1) * M * 128 : nullptr,
+                    Wf(L.dC),
+                    prev ? Wt(L.dZ) + (size_t)(t - 1) * M * 512 : nullptr,
+                    prev ? nullptr : io->dh0, prev ? 1 : 0, M, 64,
+                    part && prev ? part + (size_t)(t - 1) * ntj * 512 : nullptr};
+        return for_tile<BpttTiles>(tile_id, (int)AAA_E_ARG, [&](auto tile) -> int {
+          using Tl = decltype(tile);
+          using CK = typename Tl::template Cfg<T>;
+          if constexpr (!Tl::template serves<T, GT>()) {
+            // e.g. bf16 with fp32 gate storage and a tile that exists for fp16 gates only: fail loudly, never fall back
+            return fail(AAA_E_LAUNCH, "AAA_BPTT_TILE %d: no kernel for this operand / gate storage type", tile_id);
+          } else if constexpr (Tl::split != SplitK::None) {
+            if (!L.dhs) return fail(AAA_E_ARG, "AAA_BPTT_TILE %d: split-K needs B*P < 8192 (got %d)", bwd_tile, M);
+            const int ns = splitk_slices(4608, CK::BK, bptt_splitk());   // as launch_pipe rounds it
+            float* dhp = Wf(L.dhs);
+            if constexpr (Tl::split == SplitK::SliceFix) {   // the last slice of each tile runs the gate backward
+              int* cnt = (int*)(ws + L.dhs + (size_t)std::max(kBpttSplitMax * 128, 4 * 512) * M * 4);
+              const EpiSliceFix<EB> ef{dhp, 128, 128, M, (size_t)M * 128, ns, cdiv(M, 32), cnt, ep};   // (ep.part: null, fixk)
+              HIPCHK((step_gemm_splitk<CK>(WdTh, 4608, 128, dzt, g, M, dz_bytes, ef, 128, 4608, st, ns, Tl::ILV)));
+            } else {   // K-slice partials, then the gate backward
+              const EpiSliceT es{dhp, 128, 128, M, (size_t)M * 128};
+              HIPCHK((step_gemm_splitk<CK>(WdTh, 4608, 128, dzt, g, M, dz_bytes, es, 128, 4608, st, ns, Tl::ILV)));
+              HIPCHK((gate_bwd_last<T, GT>(M, bj, Wf(L.dO) + (size_t)(t - 1) * M * 128, dhp,
+                                           (const GT*)(ws + L.Gt) + (size_t)(t - 1) * M * 512,
+                                           Wf(L.Cst) + (size_t)(t - 1) * M * 128, Wf(L.Cst) + (size_t)t * M * 128, Wf(L.dC),
+                                           Wt(L.dZ) + (size_t)(t - 1) * M * 512,
+                                           part ? part + (size_t)(t - 1) * ntj * 512 : nullptr, st, ns, (size_t)M * 128)));
+            }
+          } else {
+            HIPCHK((step_gemm<CK, Tl::stage != Stage::Reg, T, T, EB, Tl::NBUF, Tl::ILV>(WdTh, 4608, 128, dzt, g, M, dz_bytes, ep,
+                                                                                        128, 4608, st)));
           }
-        }
+          return AAA_OK;
+        });
       };
-      const hipError_t e = g16 ? step(_Float16{}) : step(float{});
-      HIPCHK(e);
+      if (const int rc = g16 ? step(_Float16{}) : step(float{})) return rc;
       if (prev)
         if (const int rc = fix(t)) return rc;
     }

@@ -187,7 +187,6 @@ static int forward_tail(const Layout& L, const aaa_io* io, hipStream_t st, const
 
 template <typename T>
 int forward_impl(const Layout& L, const aaa_io* io, hipStream_t st, int phases, const float* reset) {
-  using C = CfgFor<T>;
   // bf16 path: the fp32 tail GEMMs on the bf16 MFMA with split operands (AAA_TAIL_SPLIT3=0: fp32 MFMA)
   TailPrecision tail_prec(std::is_same<T, __bf16>::value && env_int("AAA_TAIL_SPLIT3", 1),
                           std::is_same<T, float>::value && f32_split6());
@@ -233,6 +232,9 @@ int forward_impl(const Layout& L, const aaa_io* io, hipStream_t st, int phases, 
   // no CORE (aaa_forward_phases, fp32): the recurrence's products are already in
   // Gt / Cst / Hs / XH (aaa_core_import)
   if (!(phases & AAA_FWD_CORE)) return forward_tail<T>(L, io, st, reset);
+  // the h-part tile of the per-step chain below (looked up here: an unknown id is refused whichever kernel runs)
+  const int fwd_tile = step_tile((long)(512 / 32) * cdiv(M, 32), "AAA_STEP_TILE", false, L.dt == AAA_BF16);
+  if (fwd_tile < 0) return tile_unknown("AAA_STEP_TILE");
   if constexpr (std::is_same<T, float>::value) {
     // (a mask: the frame-group kernels' RST variants where they exist, recur_f32.h f32_fwd_resets, else the
     // per-step kernels below)
@@ -368,7 +370,6 @@ int forward_impl(const Layout& L, const aaa_io* io, hipStream_t st, int phases, 
     if (rc) return rc;
     if (ax) HIPCHK(record_event(ax, &xev[k]));
   }
-  const int fwd_tile = step_tile((long)(512 / 32) * cdiv(M, 32), "AAA_STEP_TILE", false);
   const uint32_t xh_bytes = (uint32_t)((size_t)M * 192 * L.esz);  // one step slice of XH
   for (int t = 0; t < L.T; ++t) {  // ConvLSTM recurrence (attention.py:110-126): h-part only
     if (ax && t % cs == 0) HIPCHK(hipStreamWaitEvent(st, xev[t / cs], 0));   // x-part of steps [t, t+cs) done
@@ -386,40 +387,11 @@ int forward_impl(const Layout& L, const aaa_io* io, hipStream_t st, int phases, 
     TimerScope tim(AAA_TIMER_FWD_STEP, st, 2.0 * M * 512 * 1152, strf("%s h-part step (x-part batched), K=1152, tile %d [kernel: EpiConvLstmFwd]%s", std::is_same<T, float>::value ? "fp32" : "bf16", fwd_tile, reset ? ", resets" : ""));
     const T* WpH = (const T*)(pk + L.k_WpH);
     const T* xh = Wt(L.XH) + (size_t)t * M * 192;
-    hipError_t e;
-    switch (fwd_tile) {
-      case 1: case 2: e = step_gemm<CfgKFor<T>, false>(WpH, 1152, 512, xh, g, M, xh_bytes, ep, 512, 1152, st); break;
-      case 3: e = step_gemm<Cfg64For<T>, false>(WpH, 1152, 512, xh, g, M, xh_bytes, ep, 512, 1152, st); break;
-      case 4:   // 128x64, 8 waves
-        e = step_gemm<CfgSFor<T>, true>(WpH, 1152, 512, xh, g, M, xh_bytes, ep, 512, 1152, st);
-        break;
-      case 7: e = step_gemm<C, true>(WpH, 1152, 512, xh, g, M, xh_bytes, ep, 512, 1152, st); break;
-      case 5: e = step_gemm<CfgKFor<T>, true>(WpH, 1152, 512, xh, g, M, xh_bytes, ep, 512, 1152, st); break;
-      case 6: e = step_gemm<Cfg64For<T>, true>(WpH, 1152, 512, xh, g, M, xh_bytes, ep, 512, 1152, st); break;
-      case 12:   // 32x64 BK64, 2-way in-WG split-K, 3-stage ring
-        e = step_gemm<CfgKFor<T>, true, T, T, EpiConvLstmFwd<T>, 3, true>(WpH, 1152, 512, xh, g, M, xh_bytes, ep, 512,
-                                                                          1152, st);
-        break;
-      case 14:   // 32x32 BK64, 4-way in-WG split-K, 3-stage ring
-        e = step_gemm<GemmCfg<T, 32, 32, 64, 1, 1, 4>, true, T, T, EpiConvLstmFwd<T>, 3, true>(WpH, 1152, 512, xh, g, M,
-                                                                                              xh_bytes, ep, 512, 1152, st);
-        break;
-      case 17:   // 64x32 BK64, 2-way in-WG split-K, 3-stage ring
-        e = step_gemm<GemmCfg<T, 64, 32, 64, 2, 1, 2>, true, T, T, EpiConvLstmFwd<T>, 3, true>(WpH, 1152, 512, xh, g, M,
-                                                                                              xh_bytes, ep, 512, 1152, st);
-        break;
-      case 25:   // 64x64 BK64, 2-way in-WG split-K (8 waves), 2-stage ring
-        e = step_gemm<GemmCfg<T, 64, 64, 64, 2, 2, 2>, true>(WpH, 1152, 512, xh, g, M, xh_bytes, ep, 512, 1152, st);
-        break;
-      case 26:   // 64x64 BK128, 2-way in-WG split-K (8 waves), 2-stage ring
-        e = step_gemm<GemmCfg<T, 64, 64, 128, 2, 2, 2>, true>(WpH, 1152, 512, xh, g, M, xh_bytes, ep, 512, 1152, st);
-        break;
-      case 18:   // 64x64 BK64, 2x2 waves, 3-stage ring
-        e = step_gemm<Cfg64For<T>, true, T, T, EpiConvLstmFwd<T>, 3, true>(WpH, 1152, 512, xh, g, M, xh_bytes, ep, 512,
-                                                                           1152, st);
-        break;
-      default: e = step_gemm<C, false>(WpH, 1152, 512, xh, g, M, xh_bytes, ep, 512, 1152, st); break;
-    }
+    const hipError_t e = for_tile<FwdTiles>(fwd_tile, hipErrorInvalidValue, [&](auto tile) {
+      using Tl = decltype(tile);
+      return step_gemm<typename Tl::template Cfg<T>, Tl::stage != Stage::Reg, T, T, EpiConvLstmFwd<T>, Tl::NBUF, Tl::ILV>(
+          WpH, 1152, 512, xh, g, M, xh_bytes, ep, 512, 1152, st);
+    });
     HIPCHK(e);
   }
   return forward_tail<T>(L, io, st, reset);
