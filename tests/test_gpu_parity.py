@@ -696,3 +696,98 @@ def test_uint8_frames_match_fp32_frames(cuda, conv_dtype):
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
     for n in outs[0][2]:
         assert rel_err(outs[0][2][n].numpy(), outs[1][2][n].numpy()) < 1e-5, n
+
+
+# The backward in one call (BWD_ALL) and in three (HEAD, CORE, VISION: how the learner issues it under data
+# parallelism, learner.py _backward).  Between the phases the library hands over: whether the vision backward
+# ran with the CORE phase's chunks, the ConvLSTM gradients' unpack (left to the VISION phase's launch when both
+# run in one call) and whether the BPTT launch computed dx itself (the frame-group / frame-resident kernels).
+# name: (conv_dtype, stateful core + episode starts, env, H, W, grid, uint8 frames); B = 2, T = 3
+PHASE_CASES = {
+    "fp32": ("fp32", False, {}, 64, 64, (8, 8), False),
+    "fp32 frame-group": ("fp32", False, {"AAA_F32_FRAMES": "8"}, 64, 64, (8, 8), False),
+    "fp32 stateful resets": ("fp32", True, {}, 64, 64, (8, 8), False),
+    "fp32 stateful resets frame-group": ("fp32", True, {"AAA_F32_FRAMES": "8"}, 64, 64, (8, 8), False),
+    "bf16": ("bf16", False, {}, 64, 64, (8, 8), False),
+    "bf16 frame-resident": ("bf16", False, {"AAA_FRAMES_FWD": "1", "AAA_FRAMES_BWD": "1"}, 84, 84, (11, 11), True),
+}
+
+
+@pytest.mark.parametrize("case", sorted(PHASE_CASES))
+def test_backward_phases_match_one_call(cuda, monkeypatch, case):
+    """Both ways meet the oracle check of their configuration (test_unroll_vs_oracle_fp32: 1e-4;
+    test_gpu_resets.py test_stateful_core_vs_reference: 1e-4 against reset_ref, one episode start at t = 0
+    and one inside the unroll; _bf16_checked: 2e-2 against the mask-matched bf16 oracle), and what is not
+    an atomic sum -- dh0, dc0, dcore_h0, dcore_c0 -- is bit-identical between them."""
+    import reset_ref
+    dtype, stateful, env, H, W, grid, u8 = PHASE_CASES[case]
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    T, B = 3, 2
+    ag = attention.Agent(18, grid=grid, conv_dtype=dtype, stateful_core=stateful)
+    detinit.load_into(ag, detinit.deterministic_params(0, 18, 4))
+    ag.to(cuda)
+    r = ag._runner(B, T, H, W, cuda, stateful, u8)
+    S = ag._basis_for(r.h, r.w, H, W, cuda)
+    flat, packed = ag._packed_params(r, list(ag.parameters()))
+    X = _frames(T, B, H, W).to(cuda)
+    if u8:
+        X = X.to(torch.uint8)
+    Gl, Gv = (g.to(cuda) for g in _cot(T, B))
+    mask = ch = cc = Gc = None
+    if stateful:
+        mask = torch.zeros(T, B)
+        mask[0, 1] = mask[2, 0] = 1.0
+        ch, cc, Gc = (torch.from_numpy(detinit.cotangent(s, (B, 256))).clone() for s in (51, 52, 53))
+    kw = dict(reset=None if mask is None else mask.to(cuda))
+
+    def run(split):
+        """(logits, values, attn, grads by name), the state cotangents, the core state out, the ReLU masks."""
+        ws = r.new_workspace()
+        fwd = r.forward(flat, packed, S, X, ws, core=(ch.to(cuda), cc.to(cuda)) if stateful else None, **kw)
+        relu = r.relu_masks(ws) if dtype == "bf16" else None
+        bkw = dict(want_state_grads=True, want_core_grads=stateful, dcore=(Gc.to(cuda), Gc.to(cuda)) if stateful else None,
+                   **kw)
+        if split:
+            grads = torch.empty(r.n_params, device=cuda)
+            got = {ph: r.backward(flat, packed, S, X, ws, Gl, Gv, grads=grads, phases=ph, **bkw)
+                   for ph in (N.BWD_HEAD, N.BWD_CORE, N.BWD_VISION)}
+            state = got[N.BWD_CORE][1:3] + got[N.BWD_HEAD][3:]   # each from the phase that writes it
+        else:
+            got = r.backward(flat, packed, S, X, ws, Gl, Gv, **bkw)
+            grads, state = got[0], got[1:]
+        torch.cuda.synchronize()
+        assert N.pair_status(clear=True) == 0
+        named = list(ag.named_parameters())
+        g = {n: t.view_as(p).cpu() for (n, p), t in zip(named, grads.split([p.numel() for _, p in named]))}
+        return (fwd[0].cpu(), fwd[1].cpu(), fwd[2].cpu(), g), [s.cpu() for s in state], [s.cpu() for s in fwd[5:]], relu
+
+    one, three = run(False), run(True)
+    if stateful:
+        P = ref_cpu.tensor_params(detinit.deterministic_params(0, 18, 4))
+        rch, rcc = ch.clone().requires_grad_(), cc.clone().requires_grad_()
+        rl, rv, ra, (_, rcore) = reset_ref.unroll(P, _frames(T, B, H, W), mask, core_state=(rch, rcc), stateful_core=True)
+        ((rl * Gl.cpu()).sum() + (rv * Gv.cpu()).sum() + (rcore[0] * Gc).sum() + (rcore[1] * Gc).sum()).backward()
+        ref, rtol = (rl.detach(), rv.detach(), ra.detach(), reset_ref.grads(P)), RTOL
+    elif dtype == "bf16":
+        assert all(torch.equal(one[3][k], three[3][k]) for k in one[3])   # the same forward: the same masks
+        ref, rtol = _oracle(T, B, conv_mode="bf16", H=H, W=W, masks=oracle_masks([one[3]], B)), 2e-2
+    else:
+        ref, rtol = _oracle(T, B, H=H, W=W), RTOL
+    for out, state, core, _ in (one, three):
+        way = f"{case}, {'three calls' if out is three[0] else 'one call'}: "
+        _compare(out, ref, rtol, way)
+        if stateful:
+            assert_close(core[0].numpy(), rcore[0].detach().numpy(), RTOL, way + "core hT")
+            assert_close(core[1].numpy(), rcore[1].detach().numpy(), RTOL, way + "core cT")
+            for got, want, n in ((state[2], rch.grad, "dcore_h0"), (state[3], rcc.grad, "dcore_c0")):
+                assert float(got[1].abs().max()) == 0.0, way + n   # row 1 starts an episode at step 0
+                assert_close(got.numpy(), want.numpy(), RTOL, way + n)
+    for a, b, n in zip(one[0][:3], three[0][:3], ("logits", "values", "attn")):
+        assert torch.equal(a, b), f"{case}: {n}"
+    for a, b, n in zip(one[1], three[1], ("dh0", "dc0", "dcore_h0", "dcore_c0")):
+        assert bool(torch.isfinite(a).all()) and torch.equal(a, b), f"{case}: {n} differs between one call and three"
+    if stateful:   # the ConvLSTM state of row 1 was not read either
+        assert float(one[1][0][1].abs().max()) == 0.0 and float(one[1][1][1].abs().max()) == 0.0
+    else:
+        assert float(one[1][0].abs().max()) > 0.0 and float(one[1][1].abs().max()) > 0.0

@@ -114,6 +114,13 @@ int* pair_flag_base(int dev);  // aaa_pair_flag's own snapshot of it, device-map
 int pair_take();            // pending reports of the current device (consumed)
 int pair_peek();            // ... (left pending)
 int pair_check();           // AAA_E_STRANDED if any are pending
+// *rep <- the current device's report word for a multi-workgroup recurrence (``what`` names its kind)
+inline int report_word(const char* what, int** rep) {
+  int dev = 0;
+  HIPCHK(hipGetDevice(&dev));
+  if (!(*rep = pair_report(dev))) return fail(AAA_E_LAUNCH, "cannot map the %s report word", what);
+  return AAA_OK;
+}
 
 // ------------------------------------------------------------ aux stream --
 // Work that is off the sequential ConvLSTM chain (the batched x-part of the
@@ -334,9 +341,16 @@ constexpr bool kAblationBuild = true;
 constexpr bool kAblationBuild = false;
 #endif   // K tiles of global loads in flight per workgroup (gemm_kernel_deep)
 
+// One operand of a tail GEMM: nrows rows of fp32 at pitch ld (all head_gemm / tail_gemm read of it).
+struct Rows {
+  const float* src;
+  int ld;
+  int nrows;
+};
+
 template <template <typename, typename, int, int, int> class LA_,
-          template <typename, typename, int, int, int> class LB_, class PA, class PB, class EP>
-static hipError_t head_gemm(const PA& pa, const PB& pb, const EP& ep, int Mi, int Nj, int K, int nsplit,
+          template <typename, typename, int, int, int> class LB_, class EP>
+static hipError_t head_gemm(const Rows& pa, const Rows& pb, const EP& ep, int Mi, int Nj, int K, int nsplit,
                             hipStream_t st) {
   const int mode = ab_int("AAA_HEAD_TILE", 0);
   const long tiles = (long)cdiv(Mi, 64) * cdiv(Nj, 64) * std::max(nsplit, 1);
@@ -443,8 +457,8 @@ k_skinny_gemm(const float* __restrict__ W, int ldw, int Mi, const float* __restr
 
 // Forward tail GEMM (row-major weights [Mi][K] x activations [Nj][K]): the
 // skinny kernel for <= kSkinnyMaxCols columns (AAA_SKINNY=0 disables), else head_gemm.
-template <class PA, class PB, class EP>
-static hipError_t tail_gemm(const PA& pa, const PB& pb, const EP& ep, int Mi, int Nj, int K, hipStream_t st) {
+template <class EP>
+static hipError_t tail_gemm(const Rows& pa, const Rows& pb, const EP& ep, int Mi, int Nj, int K, hipStream_t st) {
   if (Nj <= kSkinnyMaxCols && K % 4 == 0 && pa.ld % 4 == 0 && pb.ld % 4 == 0 && ab_int("AAA_SKINNY", 1)) {
     const int blocks = cdiv(cdiv(Mi, 4), 4);
     if (Nj == 1)

@@ -241,10 +241,8 @@ int forward_impl(const Layout& L, const aaa_io* io, hipStream_t st, int phases, 
     int Gf = f32_frames(L);
     if (reset && Gf && !f32_fwd_resets(f32_split6(), Gf, L.P)) Gf = 0;
     if (const int G = Gf) {   // one frame-group launch for all T steps, x-part included (recur_f32.h)
-      int dev = 0;
-      HIPCHK(hipGetDevice(&dev));
-      int* rep = pair_report(dev);
-      if (!rep) return fail(AAA_E_LAUNCH, "cannot map the frame-group report word");
+      int* rep = nullptr;
+      if (const int rc = report_word("frame-group", &rep)) return rc;
       RecF32Params rp{(const float*)(pk + L.k_Wf32), (const float*)(pk + L.k_bl), Wf(L.XH), Wf(L.Cst), Wf(L.Hs),
                       Wf(L.Gt), (int*)(ws + L.rflags), rep, pair_budget(L.T), L.T, L.B, L.h, L.w, L.P,
                       io->h0 ? 0 : 1, {}};
@@ -281,10 +279,8 @@ int forward_impl(const Layout& L, const aaa_io* io, hipStream_t st, int phases, 
       using GT = decltype(gtag);
       if constexpr (!std::is_same<T, float>::value) {
         if (const int NBd = frames_band(L)) {   // one band-mode launch for all T steps (recur.h BAND)
-          int dev = 0;
-          HIPCHK(hipGetDevice(&dev));
-          int* rep = pair_report(dev);
-          if (!rep) return fail(AAA_E_LAUNCH, "cannot map the band-mode report word");
+          int* rep = nullptr;
+          if (const int rc = report_word("band-mode", &rep)) return rc;
           RecFwdParams<GT> rp{(const __bf16*)(pk + L.k_Wfr), (const float*)(pk + L.k_bl), Wt(L.XH), Wf(L.Cst),
                               nullptr, (GT*)(ws + L.Gt), (int*)(ws + L.rflags), L.T, L.B, L.h, L.w, L.P,
                               rep, pair_budget(L.T), rec_stagger("AAA_REC_STAGGER_FWD")};
@@ -297,11 +293,8 @@ int forward_impl(const Layout& L, const aaa_io* io, hipStream_t st, int phases, 
         }
         if (const int G = frames_fwd(L)) {   // one frame-resident launch for all T steps (recur.h)
           int* rep = nullptr;
-          if (G == 2) {
-            int dev = 0;
-            HIPCHK(hipGetDevice(&dev));
-            if (!(rep = pair_report(dev))) return fail(AAA_E_LAUNCH, "cannot map the paired-kernel report word");
-          }
+          if (G == 2)
+            if (const int rc = report_word("paired-kernel", &rep)) return rc;
           RecFwdParams<GT> rp{(const __bf16*)(pk + L.k_Wfr), (const float*)(pk + L.k_bl), Wt(L.XH), Wf(L.Cst),
                               nullptr, (GT*)(ws + L.Gt), (int*)(ws + L.rflags), L.T, L.B, L.h, L.w, L.P,
                               rep, pair_budget(L.T), rec_stagger("AAA_REC_STAGGER_FWD")};
@@ -406,7 +399,6 @@ int forward_impl(const Layout& L, const aaa_io* io, hipStream_t st, int phases, 
 // GEMM row, so each step is five small GEMMs and one attention launch.  The
 // heads then run batched over all frames on CH[1..T].
 static int forward_tail_stateful(const Layout& L, const aaa_io* io, hipStream_t st, const float* reset) {
-  constexpr int NTF = CF::NT;
   char* ws = (char*)io->workspace;
   const char* pk = (const char*)io->packed;
   const float* prm = io->params;
@@ -419,8 +411,6 @@ static int forward_tail_stateful(const Layout& L, const aaa_io* io, hipStream_t 
   if (io->core_c0) HIPCHK(hipMemcpyAsync(CC, io->core_c0, sB, hipMemcpyDeviceToDevice, st));
   else HIPCHK(hipMemsetAsync(CC, 0, sB, st));
   HIPCHK(hipMemcpy2DAsync(AOX + 256, 512 * 4, CH, 256 * 4, 256 * 4, B, hipMemcpyDeviceToDevice, st));
-  using LRf = LdRows<float, float, CF::BI, CF::BK, NTF>;
-  using LRfj = LdRows<float, float, CF::BJ, CF::BK, NTF>;
   for (int t = 0; t < L.T; ++t) {
     const size_t f0 = (size_t)t * B;
     float* q1 = Wf(L.q1s) + f0 * 128;
@@ -439,24 +429,13 @@ static int forward_tail_stateful(const Layout& L, const aaa_io* io, hipStream_t 
       hq_ld = 512;
       cprev = Wf(L.dcc);
     }
-    {  // QueryNetwork(prev_output = h_{t-1}) (attention.py:184-198, 331)
-      LRf::Params pa{prm + L.poff[Q0W], 256, 128};
-      LRfj::Params pb{hq, hq_ld, B};
-      EpiStoreT<float> ep{q1, 128, 128, B, prm + L.poff[Q0B], 1};
-      HIPCHK((tail_gemm(pa, pb, ep, 128, B, 256, st)));
-    }
-    {
-      LRf::Params pa{prm + L.poff[Q2W], 128, qd};
-      LRfj::Params pb{q1, 128, B};
-      EpiStoreT<float> ep{q2, qd, qd, B, prm + L.poff[Q2B], 1};
-      HIPCHK((tail_gemm(pa, pb, ep, qd, B, 128, st)));
-    }
-    {
-      LRf::Params pa{prm + L.poff[Q4W], qd, qd};
-      LRfj::Params pb{q2, qd, B};
-      EpiStoreT<float> ep{Qt, qd, qd, B, prm + L.poff[Q4B], 0};
-      HIPCHK((tail_gemm(pa, pb, ep, qd, B, qd, st)));
-    }
+    // QueryNetwork(prev_output = h_{t-1}) (attention.py:184-198, 331)
+    HIPCHK(tail_gemm({prm + L.poff[Q0W], 256, 128}, {hq, hq_ld, B},
+                     EpiStoreT<float>{q1, 128, 128, B, prm + L.poff[Q0B], 1}, 128, B, 256, st));
+    HIPCHK(tail_gemm({prm + L.poff[Q2W], 128, qd}, {q1, 128, B},
+                     EpiStoreT<float>{q2, qd, qd, B, prm + L.poff[Q2B], 1}, qd, B, 128, st));
+    HIPCHK(tail_gemm({prm + L.poff[Q4W], qd, qd}, {q2, qd, B}, EpiStoreT<float>{Qt, qd, qd, B, prm + L.poff[Q4B], 0},
+                     qd, B, qd, st));
     // attention readout with this step's per-frame queries (basis logits in-kernel)
     {
       TimerScope tim(AAA_TIMER_ATTN_FWD, st, (double)B * attn_fwd_bytes(P, L.nq, L.ans_ld, L.esz), L.esz == 2 ? "k_attn_fwd_mfma, per-frame query (stateful core)" : "k_attn_fwd, per-frame query (stateful core)");
@@ -464,25 +443,17 @@ static int forward_tail_stateful(const Layout& L, const aaa_io* io, hipStream_t 
                       io->prev_action ? io->prev_action + f0 : nullptr, B, P, L.nq, Wf(L.Am) + f0 * P * L.nq,
                       Wf(L.ans) + f0 * L.ans_ld, L.ans_ld, st, qd));
     }
-    {  // answer_processor.0 + ReLU
-      LRf::Params pa{(const float*)(pk + L.k_W1p), L.ans_ld, 512};
-      LRfj::Params pb{Wf(L.ans) + f0 * L.ans_ld, L.ans_ld, B};
-      EpiStoreT<float> ep{Wf(L.hid1) + f0 * 512, 512, 512, B, prm + L.poff[A0B], 1};
-      HIPCHK((tail_gemm(pa, pb, ep, 512, B, L.ans_ld, st)));
-    }
-    {  // answer_processor.2 -> the answer half of this step's [answer | h_{t-1}] rows
-      LRf::Params pa{prm + L.poff[A2W], 512, 256};
-      LRfj::Params pb{Wf(L.hid1) + f0 * 512, 512, B};
-      EpiStoreT<float> ep{AOX + f0 * 512, 512, 256, B, prm + L.poff[A2B], 0};
-      HIPCHK((tail_gemm(pa, pb, ep, 256, B, 512, st)));
-    }
-    {  // policy_core LSTMCell from (h_{t-1}, c_{t-1}) (attention.py:356-358)
-      LRf::Params pa{(const float*)(pk + L.k_Wihhp), 512, 1024};
-      LRfj::Params pb{AOX + f0 * 512, 512, B};
-      EpiLstmCellFwdS ep{(const float*)(pk + L.k_blc), Wf(L.LG) + f0 * 1024, cprev, CC + (f0 + B) * 256,
-                         CH + (f0 + B) * 256, t + 1 < L.T ? AOX + (f0 + B) * 512 + 256 : nullptr, B};
-      HIPCHK((tail_gemm(pa, pb, ep, 1024, B, 512, st)));
-    }
+    // answer_processor.0 + ReLU
+    HIPCHK(tail_gemm({(const float*)(pk + L.k_W1p), L.ans_ld, 512}, {Wf(L.ans) + f0 * L.ans_ld, L.ans_ld, B},
+                     EpiStoreT<float>{Wf(L.hid1) + f0 * 512, 512, 512, B, prm + L.poff[A0B], 1}, 512, B, L.ans_ld, st));
+    // answer_processor.2 -> the answer half of this step's [answer | h_{t-1}] rows
+    HIPCHK(tail_gemm({prm + L.poff[A2W], 512, 256}, {Wf(L.hid1) + f0 * 512, 512, B},
+                     EpiStoreT<float>{AOX + f0 * 512, 512, 256, B, prm + L.poff[A2B], 0}, 256, B, 512, st));
+    // policy_core LSTMCell from (h_{t-1}, c_{t-1}) (attention.py:356-358)
+    HIPCHK(tail_gemm({(const float*)(pk + L.k_Wihhp), 512, 1024}, {AOX + f0 * 512, 512, B},
+                     EpiLstmCellFwdS{(const float*)(pk + L.k_blc), Wf(L.LG) + f0 * 1024, cprev, CC + (f0 + B) * 256,
+                                     CH + (f0 + B) * 256, t + 1 < L.T ? AOX + (f0 + B) * 512 + 256 : nullptr, B},
+                     1024, B, 512, st));
   }
   if (io->attn)
     HIPCHK(hipMemcpyAsync(io->attn, Wf(L.Am), (size_t)L.F * P * L.nq * 4, hipMemcpyDeviceToDevice, st));
@@ -493,7 +464,6 @@ static int forward_tail_stateful(const Layout& L, const aaa_io* io, hipStream_t 
 // LSTMCell, heads (all batched over the T*B frames, Q1) and state outputs.
 template <typename T>
 static int forward_tail(const Layout& L, const aaa_io* io, hipStream_t st, const float* reset) {
-  constexpr int NTF = CF::NT;
   char* ws = (char*)io->workspace;
   const char* pk = (const char*)io->packed;
   const float* prm = io->params;
@@ -516,36 +486,20 @@ static int forward_tail(const Layout& L, const aaa_io* io, hipStream_t st, const
   }
   TimerScope tim(AAA_TIMER_TAIL_FWD, st, (double)F * tail_fwd_flop(L), "answer MLP + LSTMCell + heads (fp32 GEMMs)");
   if (io->attn) HIPCHK(hipMemcpyAsync(io->attn, Wf(L.Am), (size_t)F * P * L.nq * 4, hipMemcpyDeviceToDevice, st));
-  using LRf = LdRows<float, float, CF::BI, CF::BK, NTF>;
-  using LRfj = LdRows<float, float, CF::BJ, CF::BK, NTF>;
-  {  // answer_processor.0 + ReLU (attention.py:277-282, 350)
-    LRf::Params pa{(const float*)(pk + L.k_W1p), L.ans_ld, 512};
-    LRfj::Params pb{Wf(L.ans), L.ans_ld, F};
-    EpiStoreT<float> ep{Wf(L.hid1), 512, 512, F, prm + L.poff[A0B], 1};
-    HIPCHK((tail_gemm(pa, pb, ep, 512, F, L.ans_ld, st)));
-  }
-  {  // answer_processor.2
-    LRf::Params pa{prm + L.poff[A2W], 512, 256};
-    LRfj::Params pb{Wf(L.hid1), 512, F};
-    EpiStoreT<float> ep{Wf(L.AO), 256, 256, F, prm + L.poff[A2B], 0};
-    HIPCHK((tail_gemm(pa, pb, ep, 256, F, 512, st)));
-  }
-  {  // policy_core LSTMCell from zero state (attention.py:354-355)
-    LRf::Params pa{(const float*)(pk + L.k_Wihp), 256, 1024};
-    LRfj::Params pb{Wf(L.AO), 256, F};
-    EpiLstmCellFwd ep{(const float*)(pk + L.k_blc), Wf(L.LG), Wf(L.LC), Wf(L.LH), F};
-    HIPCHK((tail_gemm(pa, pb, ep, 1024, F, 256, st)));
-  }
+  // answer_processor.0 + ReLU (attention.py:277-282, 350)
+  HIPCHK(tail_gemm({(const float*)(pk + L.k_W1p), L.ans_ld, 512}, {Wf(L.ans), L.ans_ld, F},
+                   EpiStoreT<float>{Wf(L.hid1), 512, 512, F, prm + L.poff[A0B], 1}, 512, F, L.ans_ld, st));
+  // answer_processor.2
+  HIPCHK(tail_gemm({prm + L.poff[A2W], 512, 256}, {Wf(L.hid1), 512, F},
+                   EpiStoreT<float>{Wf(L.AO), 256, 256, F, prm + L.poff[A2B], 0}, 256, F, 512, st));
+  // policy_core LSTMCell from zero state (attention.py:354-355)
+  HIPCHK(tail_gemm({(const float*)(pk + L.k_Wihp), 256, 1024}, {Wf(L.AO), 256, F},
+                   EpiLstmCellFwd{(const float*)(pk + L.k_blc), Wf(L.LG), Wf(L.LC), Wf(L.LH), F}, 1024, F, 256, st));
   }
   TimerScope tim(AAA_TIMER_TAIL_FWD, st, L.sc ? 0.0 : 2.0 * F * 256 * 2 * L.A, "policy/value heads + state out");
-  {  // policy / values heads (attention.py:365-367), batched over all frames
-    using LRf = LdRows<float, float, CF::BI, CF::BK, NTF>;
-    using LRfj = LdRows<float, float, CF::BJ, CF::BK, NTF>;
-    LRf::Params pa{(const float*)(pk + L.k_Whd), 256, 2 * L.A};
-    LRfj::Params pb{L.sc ? Wf(L.CH) + (size_t)L.B * 256 : Wf(L.LH), 256, F};
-    EpiHeads ep{io->logits, io->values, (const float*)(pk + L.k_bhd), L.A, F};
-    HIPCHK((tail_gemm(pa, pb, ep, 2 * L.A, F, 256, st)));
-  }
+  // policy / values heads (attention.py:365-367), batched over all frames
+  HIPCHK(tail_gemm({(const float*)(pk + L.k_Whd), 256, 2 * L.A}, {L.sc ? Wf(L.CH) + (size_t)L.B * 256 : Wf(L.LH), 256, F},
+                   EpiHeads{io->logits, io->values, (const float*)(pk + L.k_bhd), L.A, F}, 2 * L.A, F, 256, st));
   if (io->hT && L.esz == 2)   // h_{T-1} from XH slot T (the bf16 path keeps no fp32 h_t)
     HIPCHK(xh_to_state<__bf16>(M, (const __bf16*)(ws + L.XH) + (size_t)L.T * M * 192, io->hT, st));
   else if (io->hT)
