@@ -696,6 +696,25 @@ int aaa_vision_enc_bwd(const aaa_enc_desc* d, const void* packed, const void* fr
  * ABI version 11 without a bump (purely additive): probe by name. */
 int aaa_vision_enc_f32_fwd(const aaa_enc_desc* d, const float* cnn_params, const void* packed, const void* frames,
                            float* xp, float* y1, float* out, hipStream_t stream);
+/* Its backward the same way (the VISION phase's own dispatch: with split
+ * products, uint8 frames and a geometry it takes, the frame-resident
+ * k_vision_bwd_f32, else -- or with AAA_VIS_BWD_FRAMES=0 -- the layered
+ * launches): frames, dy2 (N,h*w,64) fp32, y1 and xp of the forward ->
+ * cnn_grads (39,008 fp32, cnn_params' layout, overwritten; conv2's bias
+ * gradient is the column sum of dy2), *fused (host int, may be NULL) = 1 when
+ * k_vision_bwd_f32 ran, and dy1 (N,H1*W1,32) fp32 (may be NULL): the layered
+ * launches' dY1, or the values the fused kernel committed on chip (it stores
+ * them only here, never in a learner step).  max_groups > 0 caps the fused
+ * kernel's workgroups (0: its default, one per CU at the most), so that a
+ * handful of frames can put several frames on one workgroup.  workspace:
+ * aaa_vision_enc_f32_workspace_bytes (accumulators, the fused kernel's
+ * partials, a dY1 for the layered launches when dy1 is NULL).  Recorded under
+ * AAA_TIMER_VISION_BWD with the learner's variant string.  Added after ABI
+ * version 11 without a bump (purely additive): probe by name. */
+size_t aaa_vision_enc_f32_workspace_bytes(const aaa_enc_desc* d);
+int aaa_vision_enc_f32_bwd(const aaa_enc_desc* d, const void* packed, const void* frames, const float* dy2,
+                           const float* y1, float* xp, float* dy1, float* cnn_grads, int* fused, int max_groups,
+                           void* workspace, hipStream_t stream);
 
 /* Attention readout of F frames (attention.py:319-348: K/V split + spatial
  * basis, logits K.Q, spatial_softmax :235-243, apply_alpha :246-254, answer

@@ -39,6 +39,7 @@ EXPORTS = (
     "aaa_forward_resets", "aaa_backward_resets",
     "aaa_vision_enc_f32_fwd",
     "aaa_grad_norm_scratch_bytes", "aaa_grad_norm", "aaa_grad_scale", "aaa_adam_step_clipped",
+    "aaa_vision_enc_f32_workspace_bytes", "aaa_vision_enc_f32_bwd",
 )
 # include/aaa.h enum aaa_timer
 TIMER_FWD_STEP, TIMER_BPTT_STEP, TIMER_CORE_WGRAD, TIMER_ATTN_FWD, TIMER_ATTN_BWD = 0, 1, 2, 3, 4
@@ -201,6 +202,8 @@ def load(path: str = LIB_PATH):
             "aaa_vision_enc_fwd": (I, [ctypes.POINTER(EncDesc), P, P, P, P, P, P, P]),
             "aaa_vision_enc_bwd": (I, [ctypes.POINTER(EncDesc), P, P, P, P, P, P, P, ctypes.POINTER(I), P, P]),
             "aaa_vision_enc_f32_fwd": (I, [ctypes.POINTER(EncDesc), P, P, P, P, P, P, P]),
+            "aaa_vision_enc_f32_workspace_bytes": (S, [ctypes.POINTER(EncDesc)]),
+            "aaa_vision_enc_f32_bwd": (I, [ctypes.POINTER(EncDesc), P, P, P, P, P, P, P, ctypes.POINTER(I), I, P, P]),
             "aaa_attn_fwd": (I, [I, I, I, I, P, P, P, I, P, P, P, P, P]),
             "aaa_attn_bwd": (I, [I, I, I, I, P, P, P, I, P, P, P, P, P]),
             "aaa_attn_fwd_bf16": (I, [I, I, I, I, P, I, P, P, I, P, P, P, P, P, P]),

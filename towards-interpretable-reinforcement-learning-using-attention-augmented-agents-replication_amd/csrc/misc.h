@@ -40,10 +40,15 @@ struct PackAll {
   F32Pack f32;
   // fp32: conv1 / conv2 pre-split into bf16 parts in k_vision_fwd_f32's fragment order (null: none)
   __bf16 *W1s = nullptr, *W2s = nullptr;
+  // fp32: the conv2 dgrad classes pre-split in k_vision_bwd_f32's fragment order (128 rows, nks 16; null: none)
+  __bf16* WdT2s = nullptr;
 };
 template <typename T> hipError_t pack_all(const PackAll<T>& a, hipStream_t st);
 // the two pre-split layouts alone (the vision component entries' pack)
 hipError_t pack_vis_split(const float* c1w, const float* c2w, __bf16* W1s, __bf16* W2s, hipStream_t st);
+// the packed fp32 conv2 dgrad classes (k_WdT2, [128][256]) -> their pre-split copy alone (the checker entry
+// aaa_vision_enc_f32_bwd, whose packed buffer is the vision component's and holds none)
+hipError_t pack_wdt2_split(const float* WdT2, __bf16* WdT2s, hipStream_t st);
 
 hipError_t query_pack(const float* b0, const float* W2, const float* b2, const float* W4, const float* b4, int nq,
                       float* q1, float* q2, float* Q, hipStream_t st);

@@ -1048,6 +1048,12 @@ __global__ void k_pack_vis_split(const float* __restrict__ c1w, const float* __r
     }
   }
 }
+// the conv2 dgrad classes [128 = class * 32 + c][256] (k_WdT2) pre-split for k_vision_bwd_f32
+__global__ void k_pack_wdt2_split(const float* __restrict__ WdT2, __bf16* WdT2s) {
+  const int tot = 4 * 32 * 256;
+  for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < tot; idx += gridDim.x * blockDim.x)
+    vis_split_el(WdT2[idx], idx >> 8, idx & 255, 16, WdT2s);
+}
 
 template <typename T>
 __global__ void k_pack_all(PackAll<T> a) {
@@ -1063,7 +1069,11 @@ __global__ void k_pack_all(PackAll<T> a) {
       if constexpr (std::is_same<T, float>::value)
         if (a.W2s) vis_split_el(a.Wp2[idx - n1], (idx - n1) >> 9, (idx - n1) & 511, 32, a.W2s);
     }
-    else if (idx < n3) pack_conv2_classes_el(idx - n2, a.c2w, a.WdT2);
+    else if (idx < n3) {
+      pack_conv2_classes_el(idx - n2, a.c2w, a.WdT2);
+      if constexpr (std::is_same<T, float>::value)
+        if (a.WdT2s) vis_split_el(a.WdT2[idx - n2], (idx - n2) >> 8, (idx - n2) & 255, 16, a.WdT2s);
+    }
     else if (idx < n4) pack_lstm_el(idx - n3, a.lstm, a.WpX, a.WpH, a.bl, a.WdT, a.WpXH);
     else pack_f32_el(idx - n4, a.f32);
   }
@@ -1539,6 +1549,10 @@ template <typename T>
 hipError_t pack_all(const PackAll<T>& a, hipStream_t st) {
   const long n = 32L * 256 + 64 * 512 + 4 * 32 * 256 + kPackLstmN + pack_f32_n(a.f32);
   hipLaunchKernelGGL(k_pack_all<T>, dim3(nblk(n)), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+hipError_t pack_wdt2_split(const float* WdT2, __bf16* WdT2s, hipStream_t st) {
+  hipLaunchKernelGGL(k_pack_wdt2_split, dim3(nblk(4L * 32 * 256)), dim3(256), 0, st, WdT2, WdT2s);
   return hipGetLastError();
 }
 hipError_t pack_vis_split(const float* c1w, const float* c2w, __bf16* W1s, __bf16* W2s, hipStream_t st) {

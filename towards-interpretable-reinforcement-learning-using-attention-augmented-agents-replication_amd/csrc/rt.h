@@ -32,6 +32,7 @@
 #include "vision.h"
 #include "vision_f32.h"
 #include "vision_bwd.h"
+#include "vision_bwd_f32.h"
 #include "misc.h"
 #include "optim.h"
 #include "actor.h"
@@ -75,7 +76,7 @@ struct Layout {
   int xpc;      // frames of the Xp chunk buffer (conv1's bordered RGBx operand, rebuilt per chunk)
   int qd, da, ans_in, ans_ld, ldy;
   size_t poff[NPARAM], psz[NPARAM], ptotal;
-  size_t k_Wp1, k_Wp2, k_WdT2, k_W1s, k_W2s, k_WpX, k_WpH, k_WpXH, k_Wfr, k_Wbf, k_Wf32, k_Wb32, k_Wf6, k_Wf6p, k_Wb6, k_Wx6, k_Wb6p, k_Wx6p, k_WdTl, k_WdTc, k_WdT6, k_bl, k_Wihhp, k_q1, k_q2, k_Q, k_W1p, k_Wihp, k_blc, k_Whd, k_bhd, packed;
+  size_t k_Wp1, k_Wp2, k_WdT2, k_W1s, k_W2s, k_WpX, k_WpH, k_WpXH, k_Wfr, k_Wbf, k_Wf32, k_Wb32, k_Wf6, k_Wf6p, k_Wb6, k_Wx6, k_Wb6p, k_Wx6p, k_WdTl, k_WdTc, k_WdT6, k_bl, k_Wihhp, k_q1, k_q2, k_Q, k_W1p, k_Wihp, k_blc, k_Whd, k_bhd, k_WdT2s, packed;
   size_t Xp, Y1, XH, Hs, Cst, Gt, SQ, Am, ans, hid1, AO, LG, LC, LH;
   size_t dY, dLG, dAO, dH1, dAns, dO, dQp, dQs, dC, dZ, dZp, dY2, dY1, dxb, rflags, xpart, dhs, dZ6;
   size_t gWp1, gWp2, gWpl, gbl, gW1p, gWihp, gblc, gWhd, gbhd, ws;
@@ -583,11 +584,12 @@ template <typename T>
 int vision_bwd(const Layout& L, const char* pk, const T* dy2, const T* y1, T* xp, T* dy1, int F, float* gW2,
                float* gW1, float* gb1, hipStream_t s, const void* frames = nullptr);
 // backward_impl's VISION phase on its own (rt_backward.hip), shared with aaa_vision_enc_bwd
-const char* vision_bwd_variant(bool fused);
+const char* vision_bwd_variant(bool fused, bool f32 = false, bool unpack = true);   // the timer's variant string
 template <typename T>
 int vision_bwd_alone(const Layout& L, const char* pk, const void* frames, const T* dy2, const T* y1, T* xp, T* dy1,
                      void* part, size_t part_bytes, int F, float* gW2, float* gW1, float* gb1, hipStream_t st,
-                     const void* xp_frames, bool* fused);
+                     const void* xp_frames, bool* fused, int max_groups = 0, float* dy1_out = nullptr,
+                     const void* wdt2s = nullptr);
 template <typename T>
 int backward_impl(const Layout& L, const aaa_io* io, int phases, hipStream_t st, const float* reset = nullptr);
 

@@ -442,9 +442,23 @@ int vision_bwd(const Layout& L, const char* pk, const T* dy2, const T* y1, T* xp
 // sums reduced 4 waves per 64 columns the fused kernel's fixed cost is ~30 us, below the layered
 // launches' own: C3 (20 frames per CU) 281 vs 358 us, C4 (10) 155 vs 199 us).
 // part_bytes: the room the caller lends the partials (0: the F frames' dY1 region, as the learner does).
+// fp32 (vision_bwd_f32.h, k_vision_bwd_f32): the split-product path (f32_split6) on uint8 observations
+// with the same switches; its partials (one per workgroup, vbwd_f32_groups: up to one per frame, which the
+// dY1 region cannot hold) go to the frames' Xp region, which the fused path never reads (part_bytes 0: the
+// F frames' images, or the chunk buffer's L.xpc); a region too small for the ideal grid runs fewer
+// workgroups, and none at all (room for no partial) keeps the layered launches.  AAA_VBWD_MINF is 1 here (at
+// least one frame per CU): below that the kernel's fixed cost loses to the layered launches (class time in a
+// learner step, fused / layered: F = 32 78.6 / 53.8 us, F = 20 77.6 / 50.4 us; C2's 640 frames 126.9 / 172.8 us).
+static size_t vbwd_f32_room(const Layout& L, int F, size_t part_bytes) {
+  return part_bytes ? part_bytes : (size_t)(L.xpc < L.F ? L.xpc : F) * (L.H + 2) * (L.W + 2) * 4 * 4;
+}
 template <typename T>
 static bool vbwd_on(const Layout& L, int F, size_t part_bytes = 0) {
-  if constexpr (!std::is_same<T, __bf16>::value) {
+  if constexpr (std::is_same<T, float>::value) {
+    return f32_split6() && L.fu8 && vbwd_f32_fits(L.H, L.W, L.H1, L.W1, L.h, L.w) && env_int("AAA_VIS_FRAMES", 1) &&
+           env_int("AAA_VIS_BWD_FRAMES", 1) && F >= env_int("AAA_VBWD_MINF", 1) * device_cus() &&
+           vbwd_f32_groups(F, device_cus(), vbwd_f32_room(L, F, part_bytes)) >= 1;
+  } else if constexpr (!std::is_same<T, __bf16>::value) {
     (void)L; (void)F; (void)part_bytes;
     return false;
   } else {
@@ -458,9 +472,16 @@ static bool vbwd_on(const Layout& L, int F, size_t part_bytes = 0) {
 // the partials in the frames' dY1 region (unused on this path)
 template <typename T>
 static int vbwd_run(const Layout& L, const char* pk, const void* frames, int f0, int F, const T* dy2, const T* y1,
-                    T* dy1, float* gW2, float* gW1, float* gb1, hipStream_t s) {
-  if constexpr (!std::is_same<T, __bf16>::value) {
-    return fail(AAA_E_ARG, "the frame-resident vision backward is bf16 only");
+                    T* dy1, float* gW2, float* gW1, float* gb1, hipStream_t s, size_t part_bytes = 0,
+                    int max_groups = 0, float* dy1_out = nullptr, const void* wdt2s = nullptr) {
+  if constexpr (std::is_same<T, float>::value) {   // dy1: the partials' room (part_bytes of it)
+    VisBwdF32Params vp{(const char*)frames + (size_t)f0 * L.H * L.W * 3, dy2, y1,
+                       (const bf16x8*)(wdt2s ? wdt2s : pk + L.k_WdT2s),
+                       dy1, dy1_out, F, L.H, L.W, L.H1, L.W1, L.h, L.w};
+    HIPCHK(vision_bwd_frames_f32(vp, vbwd_f32_groups(F, device_cus(), part_bytes, max_groups), gW2, gW1, gb1, s));
+    return AAA_OK;
+  } else if constexpr (!std::is_same<T, __bf16>::value) {
+    return fail(AAA_E_ARG, "the frame-resident vision backward is bf16 / fp32 only");
   } else {
     VisBwdParams vp{(const char*)frames + (size_t)f0 * L.H * L.W * 3 * (L.fu8 ? 1 : 4), dy2, y1,
                     (const __bf16*)(pk + L.k_WdT2), (float*)dy1, F, L.H, L.W, L.H1, L.W1, L.h, L.w};
@@ -474,17 +495,29 @@ static int vbwd_run(const Layout& L, const char* pk, const void* frames, int f0,
 // part_bytes of room; 0 = dy1, the F frames' dY1 region), else the layered launches over all F frames
 // (xp_frames: the observation the Xp chunk buffer is rebuilt from, null = xp holds every frame).
 // Accumulators zeroed by the caller; *fused (may be null) <- which of the two ran.
-const char* vision_bwd_variant(bool fused) {
-  return fused ? "frame-resident conv2 wgrad + dgrad + conv1 wgrad [kernel: k_vision_bwd_frames], grad unpack"
-               : "conv2 wgrad + dgrad, conv1 wgrad, grad unpack";
+// (fp32: the partials default to xp, the frames' Xp region; max_groups > 0 caps the workgroups and dy1_out
+// receives the dY1 the fused kernel committed, wdt2s replaces the layout's pre-split dgrad weights -- all three
+// for the checker entry aaa_vision_enc_f32_bwd)
+const char* vision_bwd_variant(bool fused, bool f32, bool unpack) {
+  static const char* const v[3][2] = {
+      {"conv2 wgrad + dgrad, conv1 wgrad", "conv2 wgrad + dgrad, conv1 wgrad, grad unpack"},
+      {"frame-resident conv2 wgrad + dgrad + conv1 wgrad [kernel: k_vision_bwd_frames]",
+       "frame-resident conv2 wgrad + dgrad + conv1 wgrad [kernel: k_vision_bwd_frames], grad unpack"},
+      {"frame-resident conv2 wgrad + dgrad + conv1 wgrad [kernel: k_vision_bwd_f32]",
+       "frame-resident conv2 wgrad + dgrad + conv1 wgrad [kernel: k_vision_bwd_f32], grad unpack"}};
+  return v[!fused ? 0 : f32 ? 2 : 1][unpack];
 }
 template <typename T>
 int vision_bwd_alone(const Layout& L, const char* pk, const void* frames, const T* dy2, const T* y1, T* xp, T* dy1,
                      void* part, size_t part_bytes, int F, float* gW2, float* gW1, float* gb1, hipStream_t st,
-                     const void* xp_frames, bool* fused) {
+                     const void* xp_frames, bool* fused, int max_groups, float* dy1_out, const void* wdt2s) {
   const bool on = vbwd_on<T>(L, F, part_bytes);
   if (fused) *fused = on;
-  if (on) return vbwd_run<T>(L, pk, frames, 0, F, dy2, y1, part ? (T*)part : dy1, gW2, gW1, gb1, st);
+  if (on) {   // the partials' room: the caller's, else the frames' Xp (fp32) / dY1 (bf16) region
+    constexpr bool f32 = std::is_same<T, float>::value;
+    return vbwd_run<T>(L, pk, frames, 0, F, dy2, y1, part ? (T*)part : f32 ? xp : dy1, gW2, gW1, gb1, st,
+                       f32 ? vbwd_f32_room(L, F, part_bytes) : 0, max_groups, dy1_out, wdt2s);
+  }
   const int rc = vision_bwd<T>(L, pk, dy2, y1, xp, dy1, F, gW2, gW1, gb1, st, xp_frames);
   if (rc) return rc;
   // fp32 with AAA_CONV2_DGRAD_RING=0: conv1's bias gradient by a column sum
@@ -709,8 +742,7 @@ static int chunk_vision(const BwdCtx& c, int lo, int hi, hipStream_t vs) {
   const size_t f0 = (size_t)lo * L.B;
   const bool on = vbwd_on<T>(L, F1);
   TimerScope tim(AAA_TIMER_VISION_BWD, vs, (double)F1 * vision_bwd_flop(L),
-                 on ? "frame-resident conv2 wgrad + dgrad + conv1 wgrad [kernel: k_vision_bwd_frames]"
-                    : "conv2 wgrad + dgrad, conv1 wgrad");
+                 vision_bwd_variant(on, std::is_same<T, float>::value, false));
   const void* fr = (const char*)c.io->frames + f0 * L.H * L.W * 3 * (L.fu8 ? 1 : 4);
   const bool chunked = L.xpc < L.F;   // Xp chunk buffer: rebuilt from the observation
   return vision_bwd_alone<T>(L, c.pk, fr, c.Wt<T>(L.dY2) + f0 * L.P * 64, c.Wt<T>(L.Y1) + f0 * L.P1 * 32,
@@ -1135,7 +1167,7 @@ static int vision_backward(const BwdCtx& c, int phases, const LstmGrads& core_un
   const Layout& L = c.L;
   const bool vision_here = (phases & AAA_BWD_CORE) != 0;   // done with the CORE phase's chunks
   TimerScope tim(AAA_TIMER_VISION_BWD, c.st, vision_here ? 0.0 : (double)L.F * vision_bwd_flop(L),
-                 vision_bwd_variant(vbwd_on<T>(L, L.F)));
+                 vision_bwd_variant(vbwd_on<T>(L, L.F), std::is_same<T, float>::value));
   if (!vision_here) {   // VISION alone: frame-resident, or its chunk work over all frames, here
     const int rc = vision_bwd_alone<T>(L, c.pk, c.io->frames, c.Wt<T>(L.dY2), c.Wt<T>(L.Y1), c.Wt<T>(L.Xp),
                                        c.Wt<T>(L.dY1), nullptr, 0, L.F, c.Wf(L.gWp2), c.Wf(L.gWp1),
@@ -1172,10 +1204,10 @@ template int vision_bwd<__bf16>(const Layout&, const char*, const __bf16*, const
                                 float*, float*, float*, hipStream_t, const void*);
 template int vision_bwd_alone<float>(const Layout&, const char*, const void*, const float*, const float*, float*,
                                      float*, void*, size_t, int, float*, float*, float*, hipStream_t, const void*,
-                                     bool*);
+                                     bool*, int, float*, const void*);
 template int vision_bwd_alone<__bf16>(const Layout&, const char*, const void*, const __bf16*, const __bf16*, __bf16*,
                                       __bf16*, void*, size_t, int, float*, float*, float*, hipStream_t, const void*,
-                                      bool*);
+                                      bool*, int, float*, const void*);
 template int backward_impl<float>(const Layout&, const aaa_io*, int, hipStream_t, const float*);
 template int backward_impl<__bf16>(const Layout&, const aaa_io*, int, hipStream_t, const float*);
 

@@ -531,6 +531,73 @@ int aaa_vision_enc_f32_fwd(const aaa_enc_desc* d, const float* cnn_params, const
   return r;
 }
 
+// ---- and its backward: the VISION phase's dispatch (vision_bwd_alone<float>) on caller-owned buffers ----
+struct EncF32Layout {
+  Layout L;
+  size_t gW1, gW2, part, part_bytes, dY1, Ws, ws;
+};
+static int enc_f32_layout(const aaa_enc_desc* d, EncF32Layout& E) {
+  if (!d) return fail(AAA_E_ARG, "enc desc is NULL");
+  if (d->dtype != AAA_F32) return fail(AAA_E_ARG, "vision_enc_f32: fp32 only (dtype %d)", d->dtype);
+  if (d->N < 1) return fail(AAA_E_ARG, "vision_enc_f32: need N >= 1");
+  if (d->flags & ~AAA_FLAG_FRAMES_U8) return fail(AAA_E_ARG, "vision_enc_f32: flags may hold AAA_FLAG_FRAMES_U8 only");
+  const aaa_cfg cfg{d->N, 1, d->H, d->W, 4, 18, d->dtype, d->flags};
+  const int r = build_layout(&cfg, E.L, 1);
+  if (r) return r;
+  size_t p = 0;
+  auto take = [&](size_t bytes) { size_t q = p; p = al256(p + bytes); return q; };
+  E.gW1 = take(32 * 256 * 4);
+  E.gW2 = take(64 * 512 * 4);
+  E.part_bytes = (size_t)E.L.F * kVbPart * 4;   // one partial per frame at the most
+  E.part = take(E.part_bytes);
+  E.dY1 = take((size_t)E.L.F * E.L.P1 * 32 * 4);
+  E.Ws = take(kVqWs);   // the pre-split dgrad weights: the vision component's packed buffer holds k_WdT2 only
+  E.ws = p;
+  return AAA_OK;
+}
+
+size_t aaa_vision_enc_f32_workspace_bytes(const aaa_enc_desc* d) {
+  EncF32Layout E;
+  return enc_f32_layout(d, E) ? 0 : E.ws;
+}
+
+int aaa_vision_enc_f32_bwd(const aaa_enc_desc* d, const void* packed, const void* frames, const float* dy2,
+                           const float* y1, float* xp, float* dy1, float* cnn_grads, int* fused, int max_groups,
+                           void* workspace, hipStream_t stream) {
+  EncF32Layout E;
+  int r = enc_f32_layout(d, E);
+  if (r) return r;
+  if (max_groups < 0) return fail(AAA_E_ARG, "vision_enc_f32_bwd: max_groups must be >= 0");
+  if (!packed || !frames || !dy2 || !y1 || !xp || !cnn_grads || !workspace)
+    return fail(AAA_E_ARG, "vision_enc_f32_bwd: packed/frames/dy2/y1/xp/cnn_grads/workspace must be set");
+  const void* ptrs[] = {packed, frames, dy2, y1, xp, dy1, cnn_grads, workspace};
+  for (const void* p : ptrs)
+    if (!aligned16(p)) return fail(AAA_E_ALIGN, "buffers must be 16-byte aligned");
+  if ((r = check_device())) return r;
+  const Layout& L = E.L;
+  char* ws = (char*)workspace;
+  float* gW1 = (float*)(ws + E.gW1);
+  float* gW2 = (float*)(ws + E.gW2);
+  HIPCHK(hipMemsetAsync(cnn_grads, 0, L.poff[XI_W] * 4, stream));
+  HIPCHK(hipMemsetAsync(gW1, 0, 32 * 256 * 4, stream));
+  HIPCHK(hipMemsetAsync(gW2, 0, 64 * 512 * 4, stream));
+  // conv2's bias gradient: the learner sums it where dY2 is produced (the ConvLSTM dx epilogue); here from dY2
+  HIPCHK(colsum<float>(dy2, 64, L.F * L.P, 64, cnn_grads + L.poff[C1B], stream));
+  HIPCHK(pack_wdt2_split((const float*)((const char*)packed + L.k_WdT2), (__bf16*)(ws + E.Ws), stream));
+  bool on = false;
+  {
+    TimerScope tim(AAA_TIMER_VISION_BWD, stream, (double)L.F * vision_bwd_flop(L), "");
+    r = vision_bwd_alone<float>(L, (const char*)packed, frames, dy2, y1, xp, dy1 ? dy1 : (float*)(ws + E.dY1),
+                                ws + E.part, E.part_bytes, L.F, gW2, gW1, cnn_grads + L.poff[C0B], stream, nullptr,
+                                &on, max_groups, dy1, ws + E.Ws);
+    tim.variant = vision_bwd_variant(on, true);
+    if (r) return r;
+    HIPCHK(unpack_cv(nullptr, nullptr, LstmGrads{}, gW2, cnn_grads + L.poff[C1W], gW1, cnn_grads + L.poff[C0W], stream));
+  }
+  if (fused) *fused = on ? 1 : 0;
+  return AAA_OK;
+}
+
 int aaa_vision_enc_bwd(const aaa_enc_desc* d, const void* packed, const void* frames, const void* dy2,
                        const void* y1, void* xp, void* dy1, float* cnn_grads, int* fused, void* workspace,
                        hipStream_t stream) {

@@ -85,6 +85,9 @@ int build_layout(const aaa_cfg* c, Layout& L, int min_frames) {
   L.k_q1 = take(128 * 4);                          // the constant query (Q1) and its activations
   L.k_q2 = take((size_t)L.qd * 4);
   L.k_Q = take((size_t)L.qd * 4);
+  // fp32: conv2's dgrad classes (k_WdT2) as hi / mid / lo bf16 parts in fragment order (vision_bwd_f32.h); after
+  // every other layout, so that the vision component's packed prefix (aaa_vision_cnn_packed_bytes) stays as it was
+  L.k_WdT2s = take(e == 4 ? kVqWs : 0);
   L.packed = p;
   // workspace
   p = 0;

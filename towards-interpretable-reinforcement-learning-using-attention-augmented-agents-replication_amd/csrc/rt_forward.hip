@@ -14,6 +14,7 @@ int pack_impl(const Layout& L, const float* prm, char* pk, hipStream_t st) {
   a.Wp1 = (T*)(pk + L.k_Wp1); a.Wp2 = (T*)(pk + L.k_Wp2); a.WdT2 = (T*)(pk + L.k_WdT2);
   if constexpr (std::is_same<T, float>::value) {   // the frame-resident fp32 encoder's pre-split weights (vision_f32.h)
     a.W1s = (__bf16*)(pk + L.k_W1s); a.W2s = (__bf16*)(pk + L.k_W2s);
+    a.WdT2s = (__bf16*)(pk + L.k_WdT2s);
   }
   for (int g = 0; g < 4; ++g) {
     a.lstm.wx[g] = prm + L.poff[XI_W + 3 * g];

@@ -435,6 +435,29 @@ class EncF32Runner:
                 "vision_enc_f32_fwd")
         return xp, y1, out
 
+    def backward(self, packed, frames, dy2, y1, xp, max_groups: int = 0):
+        """dy2 (N,h*w,64) fp32, y1 and xp of ``forward`` -> (flat fp32 grads (39,008), dy1
+        (N,H1,W1,32) fp32: the layered launches' or what the fused kernel committed on chip,
+        pre-filled with NaN, fused).  ``max_groups`` > 0 caps the fused kernel's workgroups."""
+        dev = self.device
+        want = torch.uint8 if self.u8 else torch.float32
+        if frames.dtype != want or tuple(frames.shape) != (self.N, self.H, self.W, 3):
+            raise ValueError(f"frames must be {want} of shape {(self.N, self.H, self.W, 3)}")
+        if dy2.dtype != torch.float32 or tuple(dy2.shape) != (self.N, self.h * self.w, 64):
+            raise ValueError("dy2 must be float32 (N, h*w, 64)")
+        frames, dy2 = frames.to(dev).contiguous(), dy2.to(dev).contiguous()
+        ws_bytes = self.lib.aaa_vision_enc_f32_workspace_bytes(ctypes.byref(self.desc))
+        if not ws_bytes:
+            N.check(-1, "vision_enc_f32 workspace")
+        grads = torch.empty(32 * 3 * 64 + 32 + 64 * 32 * 16 + 64, device=dev)
+        dy1 = torch.full((self.N, self.H1, self.W1, 32), float("nan"), device=dev)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        fused = ctypes.c_int(-1)
+        N.check(self.lib.aaa_vision_enc_f32_bwd(ctypes.byref(self.desc), N.ptr(packed), N.ptr(frames), N.ptr(dy2),
+                                                N.ptr(y1), N.ptr(xp), N.ptr(dy1), N.ptr(grads), ctypes.byref(fused),
+                                                int(max_groups), N.ptr(ws), N.stream_ptr(dev)), "vision_enc_f32_bwd")
+        return grads, dy1, bool(fused.value)
+
 
 class ActorRunner:
     """One environment step of B <= 16 rows on the actor chain (aaa_actor_step:
