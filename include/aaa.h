@@ -428,6 +428,57 @@ int aaa_adam_step_clipped(const aaa_adam_hparams* hp, int* step_dev, const float
                           float* const* exp_avg_sq, float* const* max_exp_avg_sq, const size_t* numel,
                           hipStream_t stream);
 
+/* ---- RMSProp (added after ABI 11 without a bump: additive, probe by name) ----
+ * One fused multi-tensor RMSProp step with torch.optim.RMSprop semantics
+ * (torch's _single_tensor_rmsprop op order, fp32), the optimizer IMPALA trains
+ * with: momentum 0, alpha 0.99, eps 0.01 or 0.1 inside the square root, and a
+ * learning rate annealed linearly to 0.  Per element:
+ *   g   = grads[i] * stats[1]   (only with stats: the fp32 product, then the update unchanged)
+ *   g   = -g (maximize);  g = g + weight_decay * p (weight_decay != 0)
+ *   v   = v * alpha;  v = v + (1 - alpha) * g * g
+ *   centered:  a = a + (1 - alpha) * (g - a);  s = v - a * a     else  s = v
+ *   avg = eps_in_sqrt ? sqrt(s + eps) : sqrt(s) + eps
+ *   momentum > 0:  b = b * momentum + g / avg;  p = p - lr_t * b
+ *   else:          p = p - lr_t * (g / avg)
+ * eps_in_sqrt = 0 is torch's placement of eps, 1 is TensorFlow's (IMPALA's).
+ * With momentum the buffer is torch's, with the learning rate outside it.
+ *
+ * lr_t = lr_end + (lr - lr_end) * max(0, 1 - n / anneal_steps), evaluated in
+ * double and rounded to fp32 once, where n is the number of updates applied
+ * before this one: *step_dev (one device int, as aaa_adam_step_counted keeps
+ * it), or step - 1 when step_dev is NULL (``step`` is then the count after
+ * this update, 1 on the first call, as for aaa_adam_step).  anneal_steps = 0
+ * is a constant lr.  Both counts give the same lr_t bit for bit.
+ *
+ * The update is skipped on the device -- nothing written, *step_dev not
+ * advanced, so the schedule stays where it was -- when *guard != 0 (guard may
+ * be NULL) or when stats[2] != 0 (stats: aaa_grad_norm's, or NULL: no
+ * clipping).  A coefficient stats[1] of exactly 1.0f is bit-identical to
+ * stats = NULL.  In stream order after the update *step_dev advances by one
+ * iff it was applied.
+ *
+ * Tensor i has numel[i] fp32 elements at params[i] / grads[i] / square_avg[i],
+ * at momentum_buf[i] when momentum > 0 and at grad_avg[i] when centered; an
+ * array that is not used may be NULL and is never read.  The pointer arrays
+ * are host memory, the tensors device memory, all updated in place on
+ * ``stream``.  ntensors = 0 or all-empty tensors launch no update and still
+ * count the step when step_dev is set.
+ * Refused before the device is touched (messages begin with "rmsprop"):
+ * AAA_E_ARG for a NULL hp or required array, a NULL tensor pointer with numel
+ * > 0, ntensors < 0, lr, lr_end, alpha, eps, weight_decay or momentum negative
+ * or NaN, anneal_steps < 0, step < 1 with step_dev NULL; AAA_E_ALIGN for a
+ * stats pointer that is not 16-byte aligned. */
+typedef struct aaa_rmsprop_hparams {
+  double lr, alpha, eps, weight_decay, momentum;
+  double lr_end;
+  long anneal_steps;   /* 0: constant lr */
+  int centered, maximize, eps_in_sqrt;
+} aaa_rmsprop_hparams;
+int aaa_rmsprop_step(const aaa_rmsprop_hparams* hp, long step, int* step_dev, const float* guard,
+                     const float* stats, int ntensors, float* const* params, const float* const* grads,
+                     float* const* square_avg, float* const* momentum_buf, float* const* grad_avg,
+                     const size_t* numel, hipStream_t stream);
+
 /* ---- REINFORCE loss ----
  * finish_episode's loss (reference main_mp.py:62-77) for B independent
  * episodes of T steps, on device: discounted returns R_t = r_t + gamma R_{t+1}

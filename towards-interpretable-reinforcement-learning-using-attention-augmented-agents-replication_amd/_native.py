@@ -40,6 +40,7 @@ EXPORTS = (
     "aaa_vision_enc_f32_fwd",
     "aaa_grad_norm_scratch_bytes", "aaa_grad_norm", "aaa_grad_scale", "aaa_adam_step_clipped",
     "aaa_vision_enc_f32_workspace_bytes", "aaa_vision_enc_f32_bwd",
+    "aaa_rmsprop_step",
 )
 # include/aaa.h enum aaa_timer
 TIMER_FWD_STEP, TIMER_BPTT_STEP, TIMER_CORE_WGRAD, TIMER_ATTN_FWD, TIMER_ATTN_BWD = 0, 1, 2, 3, 4
@@ -109,6 +110,13 @@ class AdamHP(ctypes.Structure):
     _fields_ = [("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double),
                 ("eps", ctypes.c_double), ("weight_decay", ctypes.c_double), ("amsgrad", ctypes.c_int),
                 ("maximize", ctypes.c_int)]
+
+
+class RmspropHP(ctypes.Structure):
+    """include/aaa.h aaa_rmsprop_hparams."""
+    _fields_ = [(n, ctypes.c_double) for n in ("lr", "alpha", "eps", "weight_decay", "momentum", "lr_end")] + [
+        ("anneal_steps", ctypes.c_long), ("centered", ctypes.c_int), ("maximize", ctypes.c_int),
+        ("eps_in_sqrt", ctypes.c_int)]
 
 
 class CellDesc(ctypes.Structure):
@@ -182,6 +190,7 @@ def load(path: str = LIB_PATH):
             "aaa_grad_norm": (I, [ctypes.c_double, I, P, P, P, P, P]),
             "aaa_grad_scale": (I, [P, I, P, P, P]),
             "aaa_adam_step_clipped": (I, [ctypes.POINTER(AdamHP), P, P, P, I, P, P, P, P, P, P, P]),
+            "aaa_rmsprop_step": (I, [ctypes.POINTER(RmspropHP), ctypes.c_long, P, P, P, I, P, P, P, P, P, P, P]),
             "aaa_core_elem_bytes": (I, [ctypes.POINTER(Cfg), ctypes.POINTER(I), ctypes.POINTER(I)]),
             "aaa_workspace_region": (I, [ctypes.POINTER(Cfg), I, ctypes.POINTER(ctypes.c_size_t),
                                          ctypes.POINTER(ctypes.c_size_t)]),
@@ -402,3 +411,32 @@ def adam_step(hp: AdamHP, step: int, params, grads, exp_avg, exp_avg_sq, max_exp
     else:
         check(load().aaa_adam_step(ctypes.byref(hp), int(step), n, arr(params), arr(grads), arr(exp_avg),
                                    arr(exp_avg_sq), mx, numel, st), "adam_step")
+
+
+def rmsprop_step(hp: RmspropHP, step: int, params, grads, square_avg, momentum_buf=None, grad_avg=None, stream=None,
+                 guard=None, step_dev=None, clip=None) -> None:
+    """One fused RMSProp launch over lists of same-length fp32 device tensors
+    (aaa_rmsprop_step).  ``momentum_buf`` is needed iff hp.momentum > 0,
+    ``grad_avg`` iff hp.centered.  ``guard``, a one-element fp32 device
+    tensor: no update when guard != 0; ``step_dev``, a one-element int32
+    device tensor: ``step`` is ignored, the learning-rate schedule reads the
+    updates applied so far from it, and it advances on the device only when
+    the update was applied; ``clip``, grad_norm()'s stats tensor: the update
+    runs on grad * clip[1] and is skipped when clip[2] != 0."""
+    n = len(params)
+    VP = ctypes.c_void_p * max(n, 1)
+    def arr(ts):
+        return VP(*[t.data_ptr() for t in ts]) if ts is not None else None
+    def one(t):
+        return t.data_ptr() if t is not None else None
+    numel = (ctypes.c_size_t * max(n, 1))(*[t.numel() for t in params])
+    for group in (grads, square_avg, momentum_buf, grad_avg):
+        assert group is None or len(group) == n
+    if step_dev is not None:
+        assert step_dev.numel() == 1 and step_dev.is_cuda and str(step_dev.dtype) == "torch.int32"
+    if clip is not None and (clip.numel() < 4 or str(clip.dtype) != "torch.float32"):
+        raise ValueError("rmsprop_step: clip must hold grad_norm()'s 4 fp32 elements")
+    st = stream if stream is not None else stream_ptr()
+    check(load().aaa_rmsprop_step(ctypes.byref(hp), int(step), one(step_dev), one(guard), one(clip), n, arr(params),
+                                  arr(grads), arr(square_avg), arr(momentum_buf), arr(grad_avg), numel, st),
+          "rmsprop_step")

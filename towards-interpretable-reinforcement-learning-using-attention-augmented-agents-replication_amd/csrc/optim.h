@@ -38,7 +38,32 @@ struct GradTable {
   int n;
 };
 
+// aaa_rmsprop_step: chunked as AdamTable is; b (momentum buffer) and a (grad_avg) are nullptr when unused
+struct RmspropTable {
+  float* p[kAdamMaxTensors];
+  const float* g[kAdamMaxTensors];
+  float* v[kAdamMaxTensors];
+  float* b[kAdamMaxTensors];
+  float* a[kAdamMaxTensors];
+  size_t numel[kAdamMaxTensors];
+  int chunk0[kAdamMaxTensors];
+  unsigned char vec[kAdamMaxTensors]; // every pointer in use 16-byte aligned
+  int n;
+};
+
+struct RmspropHost {
+  double lr, alpha, eps, weight_decay, momentum, lr_end;
+  long anneal_steps;              // 0: constant lr
+  long step;                      // the host's count after this update; read only without step_dev
+  int centered, maximize, eps_in_sqrt;
+  const float* guard = nullptr;   // as AdamHost's
+  int* step_dev = nullptr;        // updates applied so far: the schedule's n, advanced only by an applied update
+  const float* stats = nullptr;   // aaa_grad_norm's stats: g = grad * stats[1], no update (nor count) when stats[2] != 0
+};
+
 int adam_chunks(size_t numel);
+// advance: count this update on h.step_dev after the launch (the last table of a step)
+hipError_t rmsprop_launch(const RmspropTable& tab, int nchunks, const RmspropHost& h, hipStream_t st, bool advance);
 // advance: count this update on h.step_dev after the launch (the last table of a step)
 hipError_t adam_launch(const AdamTable& tab, int nchunks, const AdamHost& h, hipStream_t st, bool advance);
 // one double per workgroup to scratch[chunk_base + workgroup]; then one workgroup over all nchunks partials

@@ -157,6 +157,157 @@ hipError_t adam_launch(const AdamTable& tab, int nchunks, const AdamHost& h, hip
   return hipGetLastError();
 }
 
+// ---- RMSProp (aaa_rmsprop_step) ----
+// torch.optim.RMSprop's _single_tensor_rmsprop per element, in fp32 (the op
+// order is in include/aaa.h), with k_adam's structure, guard, clip and device
+// step counter.  The learning rate follows a linear anneal over the updates
+// APPLIED so far, so a skipped step does not move the schedule.  HBM traffic
+// of IMPALA's variant (momentum 0, not centered): 12 B read + 8 B written per
+// element; 4 + 4 more for each of the momentum buffer and grad_avg.
+struct RmspropScalars {
+  float wd, alpha, one_m_alpha, eps, momentum, lr_t;
+  int maximize, eps_in_sqrt;
+  const float* guard;
+  const int* step_dev;       // or nullptr: lr_t above holds
+  const float* stats;        // read only by k_rmsprop<true, ., .>
+  double lr, lr_end;         // the host's doubles, read only with step_dev
+  long anneal_steps;
+};
+
+// The lr of the update after n applied ones, in double.  One statement for the
+// host count and the device count; no contraction, so both round alike.
+__host__ __device__ inline double rmsprop_lr(double lr, double lr_end, long anneal_steps, double n) {
+#pragma clang fp contract(off)
+  if (anneal_steps <= 0) return lr;
+  double f = 1.0 - n / (double)anneal_steps;
+  if (f < 0.0) f = 0.0;
+  return lr_end + (lr - lr_end) * f;
+}
+
+template <bool kMom, bool kCent>
+__device__ __forceinline__ void rmsprop_elem(float& p, float g, float& v, float& b, float& a, const RmspropScalars& s) {
+  if (s.maximize) g = -g;
+  if (s.wd != 0.f) g = g + s.wd * p;
+  v = v * s.alpha;
+  v = v + s.one_m_alpha * g * g;
+  float sq = v;
+  if (kCent) {
+    a = a + s.one_m_alpha * (g - a);   // torch lerp, weight < 0.5
+    sq = v - a * a;
+  }
+  const float avg = s.eps_in_sqrt ? sqrtf(sq + s.eps) : sqrtf(sq) + s.eps;
+  if (kMom) {
+    b = b * s.momentum + g / avg;
+    p = p - s.lr_t * b;
+  } else {
+    p = p - s.lr_t * (g / avg);
+  }
+}
+
+// One workgroup's chunk of one tensor; kScale as in adam_chunk.  B is touched only with kMom, A only with kCent.
+template <bool kScale, bool kMom, bool kCent>
+__device__ __forceinline__ void rmsprop_chunk(const RmspropTable& tab, const RmspropScalars& s, float coef) {
+  const int blk = blockIdx.x;
+  int t = 0;
+  while (t + 1 < tab.n && tab.chunk0[t + 1] <= blk) ++t;
+  const size_t n = tab.numel[t];
+  const size_t base = (size_t)(blk - tab.chunk0[t]) * kAdamChunk;
+  float* __restrict__ P = tab.p[t];
+  const float* __restrict__ G = tab.g[t];
+  float* __restrict__ V = tab.v[t];
+  float* __restrict__ B = tab.b[t];
+  float* __restrict__ A = tab.a[t];
+  auto grad = [&](float g) { return kScale ? __fmul_rn(g, coef) : g; };
+  auto scalar = [&](size_t j) {
+    float be = kMom ? B[j] : 0.f, ae = kCent ? A[j] : 0.f;
+    rmsprop_elem<kMom, kCent>(P[j], grad(G[j]), V[j], be, ae, s);
+    if (kMom) B[j] = be;
+    if (kCent) A[j] = ae;
+  };
+  if (tab.vec[t]) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const size_t i = base + ((size_t)r * kAdamThreads + threadIdx.x) * kAdamVec;
+      if (i + kAdamVec <= n) {
+        const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+        f32x4 p = *reinterpret_cast<const f32x4*>(P + i);
+        const f32x4 g = *reinterpret_cast<const f32x4*>(G + i);
+        f32x4 v = *reinterpret_cast<const f32x4*>(V + i);
+        f32x4 b = kMom ? *reinterpret_cast<const f32x4*>(B + i) : zero;
+        f32x4 a = kCent ? *reinterpret_cast<const f32x4*>(A + i) : zero;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float pe = p[e], ve = v[e], be = b[e], ae = a[e];
+          rmsprop_elem<kMom, kCent>(pe, grad(g[e]), ve, be, ae, s);
+          p[e] = pe; v[e] = ve; b[e] = be; a[e] = ae;
+        }
+        *reinterpret_cast<f32x4*>(P + i) = p;
+        *reinterpret_cast<f32x4*>(V + i) = v;
+        if (kMom) *reinterpret_cast<f32x4*>(B + i) = b;
+        if (kCent) *reinterpret_cast<f32x4*>(A + i) = a;
+      } else {
+        for (size_t j = i; j < n; ++j) scalar(j);
+      }
+    }
+  } else {
+    for (int r = 0; r < kAdamVec * 4; ++r) {
+      const size_t j = base + (size_t)r * kAdamThreads + threadIdx.x;
+      if (j < n) scalar(j);
+    }
+  }
+}
+
+// k_adam's skips, in its order: the guard, then (kClip) the norm's flag, both before any load.
+template <bool kClip, bool kMom, bool kCent>
+__global__ void __launch_bounds__(kAdamThreads) k_rmsprop(RmspropTable tab, RmspropScalars s) {
+  if (s.guard && *s.guard != 0.f) return;
+  float coef = 1.f;
+  if (kClip) {
+    if (s.stats[2] != 0.f) return;
+    coef = s.stats[1];
+  }
+  if (s.step_dev) s.lr_t = (float)rmsprop_lr(s.lr, s.lr_end, s.anneal_steps, (double)(*s.step_dev));
+  if (kClip && coef != 1.f) rmsprop_chunk<true, kMom, kCent>(tab, s, coef);
+  else rmsprop_chunk<false, kMom, kCent>(tab, s, 1.f);
+}
+
+template <bool kClip, bool kMom>
+static void rmsprop_dispatch(bool cent, int nchunks, hipStream_t st, const RmspropTable& tab, const RmspropScalars& s) {
+  if (cent) hipLaunchKernelGGL((k_rmsprop<kClip, kMom, true>), dim3(nchunks), dim3(kAdamThreads), 0, st, tab, s);
+  else hipLaunchKernelGGL((k_rmsprop<kClip, kMom, false>), dim3(nchunks), dim3(kAdamThreads), 0, st, tab, s);
+}
+
+hipError_t rmsprop_launch(const RmspropTable& tab, int nchunks, const RmspropHost& h, hipStream_t st, bool advance) {
+  RmspropScalars s;
+  s.wd = (float)h.weight_decay;
+  s.alpha = (float)h.alpha;
+  s.one_m_alpha = (float)(1.0 - h.alpha);
+  s.eps = (float)h.eps;
+  s.momentum = (float)h.momentum;
+  s.lr_t = (float)rmsprop_lr(h.lr, h.lr_end, h.anneal_steps, (double)(h.step - 1));
+  s.maximize = h.maximize;
+  s.eps_in_sqrt = h.eps_in_sqrt;
+  s.guard = h.guard;
+  s.step_dev = h.step_dev;
+  s.stats = h.stats;
+  s.lr = h.lr;
+  s.lr_end = h.lr_end;
+  s.anneal_steps = h.anneal_steps;
+  if (nchunks > 0) {
+    const bool mom = h.momentum > 0.0, cent = h.centered != 0;
+    if (h.stats) {
+      if (mom) rmsprop_dispatch<true, true>(cent, nchunks, st, tab, s);
+      else rmsprop_dispatch<true, false>(cent, nchunks, st, tab, s);
+    } else {
+      if (mom) rmsprop_dispatch<false, true>(cent, nchunks, st, tab, s);
+      else rmsprop_dispatch<false, false>(cent, nchunks, st, tab, s);
+    }
+  }
+  if (h.step_dev && advance)
+    hipLaunchKernelGGL(k_adam_advance, dim3(1), dim3(64), 0, st, h.guard, h.stats, h.step_dev);
+  return hipGetLastError();
+}
+
 // ---- global gradient norm (aaa_grad_norm) ----
 // sum g^2 over every tensor, in double: the product of two fp32 values is
 // exact there, so the only rounding is the summation's (N * 2^-53 relative,

@@ -530,6 +530,58 @@ int aaa_adam_step_clipped(const aaa_adam_hparams* hp, int* step_dev, const float
                    stream, "clip: adam", stats);
 }
 
+// ---- RMSProp ----
+int aaa_rmsprop_step(const aaa_rmsprop_hparams* hp, long step, int* step_dev, const float* guard,
+                     const float* stats, int ntensors, float* const* params, const float* const* grads,
+                     float* const* square_avg, float* const* momentum_buf, float* const* grad_avg,
+                     const size_t* numel, hipStream_t stream) {
+  if (!hp) return fail(AAA_E_ARG, "rmsprop: NULL hyper-parameters");
+  if (ntensors < 0) return fail(AAA_E_ARG, "rmsprop: ntensors must be >= 0 (got %d)", ntensors);
+  if (!(hp->lr >= 0.0) || !(hp->lr_end >= 0.0) || !(hp->alpha >= 0.0) || !(hp->eps >= 0.0) ||
+      !(hp->weight_decay >= 0.0) || !(hp->momentum >= 0.0))
+    return fail(AAA_E_ARG, "rmsprop: invalid hyper-parameters (lr, lr_end, alpha, eps, weight_decay and momentum "
+                           "must be >= 0)");
+  if (hp->anneal_steps < 0) return fail(AAA_E_ARG, "rmsprop: anneal_steps must be >= 0 (got %ld)", hp->anneal_steps);
+  if (!step_dev && step < 1) return fail(AAA_E_ARG, "rmsprop: step must be >= 1 (got %ld)", step);
+  const bool mom = hp->momentum > 0.0, cent = hp->centered != 0;
+  if (ntensors > 0 && (!params || !grads || !square_avg || !numel || (mom && !momentum_buf) || (cent && !grad_avg)))
+    return fail(AAA_E_ARG, "rmsprop: NULL array (momentum > 0 needs momentum_buf, centered needs grad_avg)");
+  long nchunks = 0;   // of one table: the launch's grid
+  for (int t = 0; t < ntensors; ++t) {   // every refusal before the device
+    if (t % kAdamMaxTensors == 0) nchunks = 0;
+    if (numel[t] == 0) continue;
+    if (!params[t] || !grads[t] || !square_avg[t] || (mom && !momentum_buf[t]) || (cent && !grad_avg[t]))
+      return fail(AAA_E_ARG, "rmsprop: NULL pointer for tensor %d", t);
+    nchunks += adam_chunks(numel[t]);
+    if (nchunks > (1L << 30)) return fail(AAA_E_ARG, "rmsprop: tensor %d too large", t);
+  }
+  if (stats && !aligned16(stats)) return fail(AAA_E_ALIGN, "rmsprop: stats must be 16-byte aligned");
+  int r = check_device();
+  if (r) return r;
+  RmspropHost h{hp->lr, hp->alpha, hp->eps, hp->weight_decay, hp->momentum, hp->lr_end, hp->anneal_steps,
+                step_dev ? 1 : step, cent ? 1 : 0, hp->maximize ? 1 : 0, hp->eps_in_sqrt ? 1 : 0, guard, step_dev, stats};
+  for (int t0 = 0; t0 < ntensors; t0 += kAdamMaxTensors) {
+    RmspropTable tab;
+    memset(&tab, 0, sizeof tab);
+    int nch = 0;
+    for (int t = t0; t < std::min(ntensors, t0 + kAdamMaxTensors); ++t) {
+      if (numel[t] == 0) continue;
+      const int i = tab.n++;
+      tab.p[i] = params[t]; tab.g[i] = grads[t]; tab.v[i] = square_avg[t];
+      tab.b[i] = mom ? momentum_buf[t] : nullptr;
+      tab.a[i] = cent ? grad_avg[t] : nullptr;
+      tab.numel[i] = numel[t];
+      tab.chunk0[i] = nch;
+      tab.vec[i] = aligned16(params[t]) && aligned16(grads[t]) && aligned16(square_avg[t]) &&
+                   (!tab.b[i] || aligned16(tab.b[i])) && (!tab.a[i] || aligned16(tab.a[i]));
+      nch += adam_chunks(numel[t]);
+    }
+    HIPCHK(rmsprop_launch(tab, nch, h, stream, t0 + kAdamMaxTensors >= ntensors));
+  }
+  if (ntensors == 0 && step_dev) HIPCHK(rmsprop_launch(RmspropTable{}, 0, h, stream, true));
+  return AAA_OK;
+}
+
 int aaa_reinforce(int T, int B, int A, const float* logits, const int* actions, const float* rewards, double gamma,
                   float* loss, float* returns_norm, float* dlogits, hipStream_t stream) {
   if (T < 1 || B < 1 || A < 1) return fail(AAA_E_ARG, "reinforce: need T, B, A >= 1 (T=%d B=%d A=%d)", T, B, A);

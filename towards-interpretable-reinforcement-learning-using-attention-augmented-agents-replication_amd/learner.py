@@ -29,7 +29,10 @@ lives on the device too (aaa_adam_step_counted), advanced only by an applied
 update, so a skipped step leaves the bias corrections where they were.
 ``max_grad_norm`` clips the gradients by their global norm inside that update
 (aaa_grad_norm, aaa_adam_step_clipped) and skips it the same way when a
-gradient is inf or NaN.  The
+gradient is inf or NaN.  ``optimizer="rmsprop"`` puts the fused RMSProp
+(aaa_rmsprop_step: IMPALA's optimizer) in Adam's place behind the same guard,
+counter and clip; its learning rate anneals over the updates the counter says
+were applied, so a skipped step does not move the schedule either.  The
 learner's runner defers the API's own stranded check (AAA_FLAG_DEFER_STRANDED):
 no rank can raise between its collectives and leave its peers waiting in an
 unmatched all-reduce; ``check_health()`` raises after the step instead.
@@ -43,16 +46,31 @@ import torch.distributed as dist
 from . import _native as N
 from . import detinit
 from .attention import SpatialBasis
-from .optim import adam_flat_
+from .optim import adam_flat_, rmsprop_flat_, rmsprop_lr
 from .parallel import allreduce_buckets, bucket_bounds
 from .runtime import UnrollRunner
 from .vtrace import episode_starts, vtrace_cotangents
 
 
 class Learner:
+    # IMPALA's RMSProp: no momentum, decay 0.99, eps 0.01 inside the square root (``rmsprop=`` overrides any of them)
+    RMSPROP_DEFAULTS = dict(alpha=0.99, eps=0.01, momentum=0.0, centered=False, eps_in_sqrt=True)
+
     def __init__(self, B: int, T: int, H: int = 84, W: int = 84, nq: int = 4, A: int = 18,
                  dtype: str = "fp32", device=None, seed: int = 0, group=None, lr: float = 1e-3,
-                 frames_u8: bool = False, max_grad_norm: float | None = None):
+                 frames_u8: bool = False, max_grad_norm: float | None = None, optimizer: str = "adam",
+                 rmsprop: dict | None = None, lr_anneal_steps: int = 0, lr_end: float = 0.0):
+        if optimizer not in ("adam", "rmsprop"):
+            raise ValueError(f"Learner: optimizer must be 'adam' or 'rmsprop' (got {optimizer!r})")
+        if optimizer == "adam" and lr_anneal_steps:
+            raise ValueError("Learner: lr_anneal_steps needs optimizer='rmsprop' (Adam's lr is constant)")
+        if int(lr_anneal_steps) != lr_anneal_steps or lr_anneal_steps < 0 or not 0.0 <= lr_end:
+            raise ValueError(f"Learner: lr_anneal_steps must be an integer >= 0 and lr_end >= 0 (got {lr_anneal_steps}, "
+                             f"{lr_end})")
+        unknown = set(rmsprop or {}) - set(self.RMSPROP_DEFAULTS)
+        if unknown:
+            raise ValueError(f"Learner: unknown rmsprop setting(s) {sorted(unknown)}; known: "
+                             f"{sorted(self.RMSPROP_DEFAULTS)}")
         self.runner = r = UnrollRunner(B, T, H, W, nq, A, dtype, device, frames_u8=frames_u8, defer_stranded=True)
         self.device = r.device
         params = detinit.deterministic_params(seed, A, nq)
@@ -71,9 +89,17 @@ class Learner:
         N.pair_flag(self.guard, base=self._pair_base)
         self._gbuf.zero_()
         self.lr = lr
-        self.exp_avg = torch.zeros_like(self.grads)
-        self.exp_avg_sq = torch.zeros_like(self.grads)
-        self.step_dev = torch.zeros(1, dtype=torch.int32, device=self.device)   # Adam updates applied
+        self.optimizer = optimizer
+        self.lr_anneal_steps, self.lr_end = int(lr_anneal_steps), float(lr_end)
+        if optimizer == "adam":
+            self.exp_avg = torch.zeros_like(self.grads)
+            self.exp_avg_sq = torch.zeros_like(self.grads)
+        else:   # only the state the variant uses (aaa_rmsprop_step never touches the rest)
+            self.rmsprop = dict(self.RMSPROP_DEFAULTS, **(rmsprop or {}))
+            self.square_avg = torch.zeros_like(self.grads)
+            self.momentum_buf = torch.zeros_like(self.grads) if self.rmsprop["momentum"] > 0 else None
+            self.grad_avg = torch.zeros_like(self.grads) if self.rmsprop["centered"] else None
+        self.step_dev = torch.zeros(1, dtype=torch.int32, device=self.device)   # optimizer updates applied
         # clip by global norm (optimizer_step reads the attribute, so it can be toggled between steps):
         # [norm, coefficient, non-finite flag, max_norm] of the last clipped step, and the norm's partials
         self.max_grad_norm = max_grad_norm
@@ -269,7 +295,7 @@ class Learner:
 
     @property
     def opt_steps(self) -> int:
-        """Adam updates applied so far (reads the device counter: syncs)."""
+        """Optimizer updates applied so far (reads the device counter: syncs)."""
         return int(self.step_dev.item())
 
     def check_health(self):
@@ -297,18 +323,35 @@ class Learner:
         wait for the comm stream; the guard slot is not part of it) goes to
         ``grad_stats``, and the update runs on ``grads * coefficient`` inside
         the same fused launch.  A norm that is not finite -- some gradient
-        element is inf or NaN -- skips the update exactly as the guard does."""
-        if self.max_grad_norm is None:
+        element is inf or NaN -- skips the update exactly as the guard does.
+
+        ``optimizer="rmsprop"``: the same launches with the fused RMSProp
+        (aaa_rmsprop_step) in Adam's place -- the guard, the device step counter
+        and the clip stats are passed alike, and the learning rate follows its
+        linear anneal over the updates the counter says were applied."""
+        clip = None
+        if self.max_grad_norm is not None:
+            if self._clip_scratch is None:
+                raise RuntimeError("aaa: the loaded library has no aaa_grad_norm (an older build under AAA_LIB); "
+                                   "max_grad_norm needs it -- there is no fallback")
+            N.grad_norm(self.max_grad_norm, [self.grads], self.grad_stats, self._clip_scratch,
+                        stream=N.stream_ptr(self.device))
+            clip = self.grad_stats
+        if self.optimizer == "rmsprop":
+            rmsprop_flat_(self.flat, self.grads, self.square_avg, 0, momentum_buf=self.momentum_buf,
+                          grad_avg=self.grad_avg, guard=self.guard, step_dev=self.step_dev, clip=clip, lr=self.lr,
+                          lr_end=self.lr_end, anneal_steps=self.lr_anneal_steps, **self.rmsprop)
+        else:
             adam_flat_(self.flat, self.grads, self.exp_avg, self.exp_avg_sq, 0, lr=self.lr, guard=self.guard,
-                       step_dev=self.step_dev)
-            return
-        if self._clip_scratch is None:
-            raise RuntimeError("aaa: the loaded library has no aaa_grad_norm (an older build under AAA_LIB); "
-                               "max_grad_norm needs it -- there is no fallback")
-        N.grad_norm(self.max_grad_norm, [self.grads], self.grad_stats, self._clip_scratch,
-                    stream=N.stream_ptr(self.device))
-        adam_flat_(self.flat, self.grads, self.exp_avg, self.exp_avg_sq, 0, lr=self.lr, guard=self.guard,
-                   step_dev=self.step_dev, clip=self.grad_stats)
+                       step_dev=self.step_dev, clip=clip)
+
+    def current_lr(self) -> float:
+        """The learning rate the next update will use: the anneal at ``opt_steps`` (constant for
+        Adam and without ``lr_anneal_steps``).  Reads the device counter: syncs; for logging,
+        outside the iteration."""
+        if self.optimizer != "rmsprop":
+            return float(self.lr)
+        return rmsprop_lr(self.opt_steps, self.lr, self.lr_end, self.lr_anneal_steps)
 
     def clip_report(self) -> dict:
         """The last clipped step's norm, coefficient, non-finite flag and

@@ -9,6 +9,11 @@ into it and back; ``step()`` is ONE fused multi-tensor HIP launch
 (csrc/optim.hip, C ABI ``aaa_adam_step``) instead of torch's seven foreach
 passes.  There is no CPU fallback: parameters must be fp32 tensors on the
 gfx950 device.
+
+``aaa_amd.optim.RMSprop`` / ``rmsprop_flat_`` are the same for
+``torch.optim.RMSprop`` (C ABI ``aaa_rmsprop_step``), the optimizer IMPALA
+trains with, with TensorFlow's placement of eps and a linear learning-rate
+anneal on the device as extensions.
 """
 from __future__ import annotations
 
@@ -19,7 +24,7 @@ from torch.autograd.graph import increment_version
 
 from . import _native as N
 
-__all__ = ["Adam", "adam_flat_", "clip_grad_norm_"]
+__all__ = ["Adam", "adam_flat_", "clip_grad_norm_", "RMSprop", "rmsprop_flat_", "rmsprop_lr"]
 
 
 class Adam(torch.optim.Optimizer):
@@ -86,6 +91,129 @@ class Adam(torch.optim.Optimizer):
                             stream=N.stream_ptr(ps[0].device))
                 _bump_versions(ps)
         return loss
+
+
+class RMSprop(torch.optim.Optimizer):
+    """Drop-in fused ``torch.optim.RMSprop`` (include/aaa.h ``aaa_rmsprop_step``): the same
+    constructor arguments, validation and per-parameter state (``step``, ``square_avg``, and
+    ``momentum_buffer`` / ``grad_avg`` only when used), so a torch state_dict loads into it and
+    back; ``step()`` is one fused launch per 48 tensors.  Keyword-only extensions:
+    ``eps_in_sqrt`` (TensorFlow's sqrt(v + eps), as IMPALA uses it, instead of torch's
+    sqrt(v) + eps) and a linear anneal of the learning rate from ``lr`` to ``lr_end`` over
+    ``anneal_steps`` updates (0: constant).  With momentum the buffer is torch's, the learning
+    rate outside it.  There is no CPU fallback."""
+
+    def __init__(self, params, lr=1e-2, alpha=0.99, eps=1e-8, weight_decay=0, momentum=0, centered=False,
+                 capturable=False, foreach=None, maximize=False, differentiable=False, *,
+                 eps_in_sqrt: bool = False, lr_end: float = 0.0, anneal_steps: int = 0):
+        if not 0.0 <= float(lr):
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= momentum:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if not 0.0 <= alpha:
+            raise ValueError(f"Invalid alpha value: {alpha}")
+        if not 0.0 <= lr_end:
+            raise ValueError(f"Invalid lr_end value: {lr_end}")
+        if int(anneal_steps) != anneal_steps or anneal_steps < 0:
+            raise ValueError(f"Invalid anneal_steps value: {anneal_steps}")
+        if differentiable:
+            raise RuntimeError("aaa_amd.optim.RMSprop: differentiable=True is not supported by the fused kernel")
+        defaults = dict(lr=lr, momentum=momentum, alpha=alpha, eps=eps, centered=centered, weight_decay=weight_decay,
+                        capturable=capturable, foreach=foreach, maximize=maximize, differentiable=differentiable,
+                        eps_in_sqrt=eps_in_sqrt, lr_end=lr_end, anneal_steps=int(anneal_steps))
+        super().__init__(params, defaults)
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        for group in self.param_groups:   # a torch.optim.RMSprop state_dict has no extension keys
+            group.setdefault("eps_in_sqrt", False)
+            group.setdefault("lr_end", 0.0)
+            group.setdefault("anneal_steps", 0)
+            for p in group["params"]:
+                st = self.state.get(p, {})
+                if len(st) != 0 and not torch.is_tensor(st["step"]):
+                    st["step"] = torch.tensor(float(st["step"]), dtype=torch.float32)
+
+    @staticmethod
+    def _hp(group) -> N.RmspropHP:
+        return _rmsprop_hp(**{k: group[k] for k in ("lr", "alpha", "eps", "weight_decay", "momentum", "centered",
+                                                     "maximize", "eps_in_sqrt", "lr_end", "anneal_steps")})
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for group in self.param_groups:
+            mom, cent = group["momentum"] > 0, bool(group["centered"])
+            by_step = defaultdict(lambda: ([], [], [], [], []))
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                if p.grad.is_sparse:
+                    raise RuntimeError("RMSprop does not support sparse gradients")
+                if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
+                    raise RuntimeError("aaa_amd.optim.RMSprop: parameters must be contiguous fp32 tensors on the "
+                                       "gfx950 device (there is no CPU fallback)")
+                st = self.state[p]
+                if len(st) == 0:
+                    st["step"] = torch.tensor(0.0, dtype=torch.float32)
+                    st["square_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    if mom:
+                        st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    if cent:
+                        st["grad_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st["step"] += 1
+                lists = by_step[int(st["step"].item())]
+                lists[0].append(p)
+                lists[1].append(p.grad.contiguous())
+                lists[2].append(st["square_avg"])
+                if mom:
+                    lists[3].append(st["momentum_buffer"])
+                if cent:
+                    lists[4].append(st["grad_avg"])
+            hp = self._hp(group)
+            for step, (ps, gs, vs, bs, as_) in by_step.items():
+                N.rmsprop_step(hp, step, ps, gs, vs, bs if mom else None, as_ if cent else None,
+                               stream=N.stream_ptr(ps[0].device))
+                _bump_versions(ps)
+        return loss
+
+
+def _rmsprop_hp(lr=1e-2, alpha=0.99, eps=1e-8, weight_decay=0.0, momentum=0.0, centered=False, maximize=False,
+                eps_in_sqrt=False, lr_end=0.0, anneal_steps=0) -> N.RmspropHP:
+    return N.RmspropHP(float(lr), float(alpha), float(eps), float(weight_decay), float(momentum), float(lr_end),
+                       int(anneal_steps), 1 if centered else 0, 1 if maximize else 0, 1 if eps_in_sqrt else 0)
+
+
+def rmsprop_lr(n: int, lr: float, lr_end: float = 0.0, anneal_steps: int = 0) -> float:
+    """The learning rate of the update after ``n`` applied ones (include/aaa.h aaa_rmsprop_step):
+    lr_end + (lr - lr_end) * max(0, 1 - n / anneal_steps) in double; anneal_steps = 0 is a constant lr."""
+    if anneal_steps <= 0:
+        return float(lr)
+    return float(lr_end) + (float(lr) - float(lr_end)) * max(0.0, 1.0 - n / anneal_steps)
+
+
+def rmsprop_flat_(params: torch.Tensor, grads: torch.Tensor, square_avg: torch.Tensor, step: int, *,
+                  momentum_buf: torch.Tensor | None = None, grad_avg: torch.Tensor | None = None,
+                  guard: torch.Tensor | None = None, step_dev: torch.Tensor | None = None,
+                  clip: torch.Tensor | None = None, **hparams) -> None:
+    """RMSProp over one flat fp32 buffer (the Learner's state_dict-ordered params): one launch.
+    ``hparams``: lr, alpha, eps, weight_decay, momentum, centered, maximize, eps_in_sqrt, lr_end,
+    anneal_steps (torch.optim.RMSprop's defaults; the last three as aaa_amd.optim.RMSprop).
+    ``momentum_buf`` is needed iff momentum > 0, ``grad_avg`` iff centered.  ``guard``,
+    ``step_dev`` and ``clip`` as for adam_flat_ (here ``clip`` does not need ``step_dev``); with
+    ``step_dev`` the anneal follows the updates applied on the device, otherwise ``step`` - 1."""
+    hp = _rmsprop_hp(**hparams)
+    N.rmsprop_step(hp, step, [params], [grads], [square_avg], None if momentum_buf is None else [momentum_buf],
+                   None if grad_avg is None else [grad_avg], stream=N.stream_ptr(params.device), guard=guard,
+                   step_dev=step_dev, clip=clip)
+    _bump_versions([params])
 
 
 def _bump_versions(ps) -> None:
