@@ -625,6 +625,92 @@ size_t aaa_actor_core_workspace_bytes(const aaa_cfg* cfg);
 int aaa_actor_step_core(const aaa_cfg* cfg, const aaa_actor_io* io, const aaa_actor_core_io* core,
                         hipStream_t stream);
 
+/* ---- actor: recording unrolls (added after ABI 11 without a bump: additive, probe by name) ----
+ * Two small calls around an actor step (aaa_actor_step, aaa_actor_step_core or
+ * aaa_forward with T = 1) assemble the time-major unroll the learner trains
+ * on, on the device: the frames, actions, behaviour log-probs, rewards and
+ * done flags of T steps, which rows start an episode at step 0, and the
+ * recurrent state BEFORE step 0 (aaa_io's h0 / c0 / core_h0 / core_c0).  The
+ * write position is a device-side cursor ``pos``, so the arguments never
+ * change from step to step and the calls can sit in a captured hipGraph with
+ * the step between them: aaa_unroll_begin, the step, aaa_unroll_record.
+ *
+ * Consecutive unrolls share one step: step T-1 of an unroll is step 0 of the
+ * next (its value is the bootstrap, bootstrap="last"), so unroll u holds the
+ * environment steps u (T-1) .. u (T-1) + T-1, and two banks alternate.  With
+ * t = pos[0] and k = pos[1] as read when the launch starts:
+ *
+ * aaa_unroll_begin, before the step:
+ *   rows with done_in[b] != 0 get zeros written into h, c (core_h, core_c): a
+ *   select, not a multiply -- a NaN state does not survive an episode end;
+ *   t == 0:    the (post-reset) state of every row is copied into bank[k]'s
+ *              h0 / c0 / core_h0 / core_c0 rows b0 + b, and
+ *              first[b0 + b] = (done_in[b] != 0);
+ *   t == T-1:  the same copy and ``first`` go to bank[1-k];
+ *   otherwise  it only resets.
+ * aaa_unroll_record, after the step:
+ *   frame, actions and logp go to slot t of bank[k];
+ *   t >= 1:    rewards[t-1] = clip(reward_in), done[t-1] = (done_in != 0);
+ *   t == T-1:  slot 0 of bank[1-k] gets the frame, action and logp too,
+ *              rewards[T-1] = done[T-1] = 0 in bank[k] (never read with
+ *              bootstrap="last"; nothing is left uninitialised), and
+ *              pos = [1, 1-k, pos[2] + 1, 0];
+ *   otherwise  pos[0] = t + 1.
+ * reward_in / done_in (B) are the result of the PREVIOUS step's action, as an
+ * environment returns them with the observation of this step; done_in = 1 on
+ * an episode's first step.  pos is 4 device ints [t, bank, unrolls completed,
+ * 0]; all zero = start (and restart).  After n steps from a zero pos,
+ * pos[2] = 0 for n < T, else 1 + (n - T) / (T - 1): a host can tell when an
+ * unroll is complete without reading the device.  Unroll u is bank[u % 2]; it
+ * is next written T-1 steps after it completed.
+ *
+ * Rows outside [b0, b0 + B) of the banks, and slots other than those named,
+ * are never touched, so several actors fill disjoint row ranges of the same
+ * banks, each with a pos of its own.  pos is read by every workgroup and
+ * written by a trailing one-workgroup launch, in stream order after them.
+ * Everything is enqueued on ``stream`` in order: no side stream, no host sync.
+ * A pos outside its range (t not in [0, T), bank not 0 or 1) makes both calls
+ * write nothing.  Frame rows move in 16-byte pieces when frame_bytes % 16 == 0
+ * (84x84, 168x168 and 210x160 frames), else byte by byte; state rows always in
+ * 16-byte pieces.
+ * Refused before the device is touched (messages begin with "unroll"):
+ * AAA_E_ARG for T < 2, B < 1, b0 < 0, b0 + B > Bu, frame_bytes == 0,
+ * state_floats % 4 != 0, core not 0 or 256, reward_clip negative or NaN, a
+ * NULL desc, io or pointer the call reads or writes (begin: pos, done_in, h,
+ * c and both banks' first, h0, c0; record: pos, frame, actions, logp,
+ * reward_in, done_in and both banks' frames, actions, logp, rewards, done;
+ * core == 256 adds core_h, core_c and the banks' core_h0, core_c0 to begin);
+ * AAA_E_ALIGN for a pos, live-state or bank-state pointer that is not 16-byte
+ * aligned, or a frames / frame pointer that is not when frame_bytes % 16 == 0. */
+typedef struct aaa_unroll_desc {
+  int T;               /* steps per unroll, >= 2; consecutive unrolls share one step */
+  int B;               /* rows this actor steps */
+  int Bu, b0;          /* rows of the unroll buffers; this actor fills rows [b0, b0 + B) */
+  size_t frame_bytes;  /* bytes of one row's observation (H*W*3 uint8) */
+  size_t state_floats; /* floats of one row's ConvLSTM h (h*w*128); multiple of 4 */
+  int core;            /* 0, or 256: floats per row of core_h / core_c */
+  double reward_clip;  /* 0: rewards stored as given; c > 0: clamped to [-c, c] (NaN stays NaN) */
+} aaa_unroll_desc;
+typedef struct aaa_unroll_bank {   /* one unroll, the layouts the learner's V-trace step takes */
+  void* frames;        /* (T, Bu, frame_bytes) uint8 */
+  int* actions;        /* (T, Bu) */
+  float *logp, *rewards, *done;   /* (T, Bu) */
+  float* first;        /* (Bu): 1 where step 0 starts an episode */
+  float *h0, *c0;      /* (Bu, state_floats): the state BEFORE step 0 */
+  float *core_h0, *core_c0;       /* (Bu, core) or NULL when core == 0 */
+} aaa_unroll_bank;
+typedef struct aaa_unroll_io {
+  aaa_unroll_bank bank[2];
+  int* pos;            /* 4 device ints, 16-B aligned: [t, bank, unrolls completed, 0]; zero = start */
+  const void* frame;   /* this step, (B, frame_bytes) */
+  const int* actions;  /* (B) */
+  const float* logp;   /* (B) */
+  const float *reward_in, *done_in;  /* (B): result of the PREVIOUS step's action; done_in = 1 on an episode's first step */
+  float *h, *c, *core_h, *core_c;    /* the actor's live state, (B, ...) */
+} aaa_unroll_io;
+int aaa_unroll_begin(const aaa_unroll_desc* d, const aaa_unroll_io* io, hipStream_t stream);   /* before the actor step */
+int aaa_unroll_record(const aaa_unroll_desc* d, const aaa_unroll_io* io, hipStream_t stream);  /* after it */
+
 /* ---- single-kernel entry points (unit tests against PyTorch fp32) ---- */
 
 /* NHWC convolution y[n,oy,ox,co] = b[co] + sum w[co,ky,kx,ci] x[n,iy,ix,ci]

@@ -41,6 +41,7 @@ EXPORTS = (
     "aaa_grad_norm_scratch_bytes", "aaa_grad_norm", "aaa_grad_scale", "aaa_adam_step_clipped",
     "aaa_vision_enc_f32_workspace_bytes", "aaa_vision_enc_f32_bwd",
     "aaa_rmsprop_step",
+    "aaa_unroll_begin", "aaa_unroll_record",
 )
 # include/aaa.h enum aaa_timer
 TIMER_FWD_STEP, TIMER_BPTT_STEP, TIMER_CORE_WGRAD, TIMER_ATTN_FWD, TIMER_ATTN_BWD = 0, 1, 2, 3, 4
@@ -104,6 +105,29 @@ VTRACE_IO_FIELDS = ("logits", "values", "actions", "rewards", "behaviour_logp", 
 class VtraceIO(ctypes.Structure):
     """include/aaa.h aaa_vtrace_io."""
     _fields_ = [(n, ctypes.c_void_p) for n in VTRACE_IO_FIELDS]
+
+
+class UnrollDesc(ctypes.Structure):
+    """include/aaa.h aaa_unroll_desc."""
+    _fields_ = [(n, ctypes.c_int) for n in ("T", "B", "Bu", "b0")] + [
+        ("frame_bytes", ctypes.c_size_t), ("state_floats", ctypes.c_size_t), ("core", ctypes.c_int),
+        ("reward_clip", ctypes.c_double)]
+
+
+UNROLL_BANK_FIELDS = ("frames", "actions", "logp", "rewards", "done", "first", "h0", "c0", "core_h0", "core_c0")
+
+
+class UnrollBank(ctypes.Structure):
+    """include/aaa.h aaa_unroll_bank."""
+    _fields_ = [(n, ctypes.c_void_p) for n in UNROLL_BANK_FIELDS]
+
+
+UNROLL_IO_FIELDS = ("pos", "frame", "actions", "logp", "reward_in", "done_in", "h", "c", "core_h", "core_c")
+
+
+class UnrollIO(ctypes.Structure):
+    """include/aaa.h aaa_unroll_io."""
+    _fields_ = [("bank", UnrollBank * 2)] + [(n, ctypes.c_void_p) for n in UNROLL_IO_FIELDS]
 
 
 class AdamHP(ctypes.Structure):
@@ -224,6 +248,8 @@ def load(path: str = LIB_PATH):
             "aaa_actor_core_workspace_bytes": (S, [CP]),
             "aaa_actor_step_core": (I, [CP, ctypes.POINTER(ActorIO), ctypes.POINTER(ActorCoreIO), P]),
             "aaa_pair_status": (I, [P, I]),
+            "aaa_unroll_begin": (I, [ctypes.POINTER(UnrollDesc), ctypes.POINTER(UnrollIO), P]),
+            "aaa_unroll_record": (I, [ctypes.POINTER(UnrollDesc), ctypes.POINTER(UnrollIO), P]),
         }
         ab_override = "AAA_LIB" in os.environ
         missing = [name for name in sig if not hasattr(lib, name)]
@@ -335,6 +361,20 @@ def pair_flag(dst, stream=None, base=None) -> None:
         if base.dtype != torch.int32 or base.device != dst.device:
             raise ValueError("pair_flag: base must be an int32 tensor on dst's device")
         check(load().aaa_pair_flag_at(dst.data_ptr(), base.data_ptr(), st), "pair_flag_at")
+
+
+def unroll_begin(desc: UnrollDesc, io: UnrollIO, stream=None) -> None:
+    """Enqueue aaa_unroll_begin (before the actor step): episode-end resets of the live state and, at an
+    unroll boundary, the state before the step into the bank it starts.  No host sync."""
+    st = stream if stream is not None else stream_ptr()
+    check(load().aaa_unroll_begin(ctypes.byref(desc), ctypes.byref(io), st), "unroll_begin")
+
+
+def unroll_record(desc: UnrollDesc, io: UnrollIO, stream=None) -> None:
+    """Enqueue aaa_unroll_record (after the actor step): the step's frame, action, logp, reward and done
+    into the banks at the device cursor io.pos, which then advances.  No host sync."""
+    st = stream if stream is not None else stream_ptr()
+    check(load().aaa_unroll_record(ctypes.byref(desc), ctypes.byref(io), st), "unroll_record")
 
 
 def _tensor_table(ts):

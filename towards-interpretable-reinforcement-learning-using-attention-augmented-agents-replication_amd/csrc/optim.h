@@ -79,5 +79,11 @@ hipError_t reinforce_launch(int T, int B, int A, const float* logits, const int*
 hipError_t vtrace_launch(const aaa_vtrace_desc& d, const aaa_vtrace_io& io, hipStream_t st);
 hipError_t sample_launch(int B, int A, const float* logits, uint64_t seed, unsigned long long* counter, int* actions,
                          float* logp, float* jac, hipStream_t st);
+// unroll.hip: the actor's unroll recorder (arguments checked by the caller); workgroups per row of each launch
+int unroll_begin_chunks(const aaa_unroll_desc& d);
+int unroll_record_chunks(const aaa_unroll_desc& d);
+hipError_t unroll_begin_launch(const aaa_unroll_desc& d, const aaa_unroll_io& io, hipStream_t st);
+// the frame rows, then the one-workgroup launch that writes the per-row scalars and advances io.pos
+hipError_t unroll_record_launch(const aaa_unroll_desc& d, const aaa_unroll_io& io, hipStream_t st);
 
 }  // namespace aaa

@@ -628,6 +628,76 @@ int aaa_sample_actions(int B, int A, const float* logits, unsigned long long see
   return AAA_OK;
 }
 
+// ---- actor unroll recorder (include/aaa.h; csrc/unroll.hip) ----
+// Every refusal of aaa_unroll_begin (record = false) / aaa_unroll_record, before the device.
+static int unroll_check(bool record, const aaa_unroll_desc* d, const aaa_unroll_io* io) {
+  const char* who = record ? "record" : "begin";
+  if (!d || !io) return fail(AAA_E_ARG, "unroll: %s: NULL desc or io", who);
+  if (d->T < 2) return fail(AAA_E_ARG, "unroll: %s: T must be >= 2 (got %d): consecutive unrolls share a step", who, d->T);
+  if (d->B < 1) return fail(AAA_E_ARG, "unroll: %s: B must be >= 1 (got %d)", who, d->B);
+  if (d->b0 < 0 || (long)d->b0 + d->B > (long)d->Bu)
+    return fail(AAA_E_ARG, "unroll: %s: rows [b0, b0 + B) = [%d, %ld) lie outside the %d rows of the banks", who, d->b0,
+                (long)d->b0 + d->B, d->Bu);
+  if (d->frame_bytes == 0) return fail(AAA_E_ARG, "unroll: %s: frame_bytes must be > 0", who);
+  if (d->state_floats % 4 != 0)
+    return fail(AAA_E_ARG, "unroll: %s: state_floats must be a multiple of 4 (got %zu)", who, d->state_floats);
+  if (d->core != 0 && d->core != 256) return fail(AAA_E_ARG, "unroll: %s: core must be 0 or 256 (got %d)", who, d->core);
+  if (!(d->reward_clip >= 0.0)) return fail(AAA_E_ARG, "unroll: %s: reward_clip must be >= 0 (0: no clipping)", who);
+  // one workgroup per 16 KB of a row: the grid of either launch stays far inside 2^31
+  if (d->frame_bytes > ((size_t)1 << 40) || d->state_floats > ((size_t)1 << 40) ||
+      (long)d->B * (record ? unroll_record_chunks(*d) : unroll_begin_chunks(*d)) > (1L << 30))
+    return fail(AAA_E_ARG, "unroll: %s: B x row size too large for one launch", who);
+  if (!io->pos || !io->done_in) return fail(AAA_E_ARG, "unroll: %s: NULL pos or done_in", who);
+  if (record) {
+    if (!io->frame || !io->actions || !io->logp || !io->reward_in)
+      return fail(AAA_E_ARG, "unroll: record: NULL frame, actions, logp or reward_in");
+    for (int k = 0; k < 2; ++k) {
+      const aaa_unroll_bank& b = io->bank[k];
+      if (!b.frames || !b.actions || !b.logp || !b.rewards || !b.done)
+        return fail(AAA_E_ARG, "unroll: record: NULL frames, actions, logp, rewards or done in bank %d", k);
+    }
+  } else {
+    if (!io->h || !io->c) return fail(AAA_E_ARG, "unroll: begin: NULL h or c");
+    if (d->core && (!io->core_h || !io->core_c)) return fail(AAA_E_ARG, "unroll: begin: core = 256 needs core_h and core_c");
+    for (int k = 0; k < 2; ++k) {
+      const aaa_unroll_bank& b = io->bank[k];
+      if (!b.first || !b.h0 || !b.c0) return fail(AAA_E_ARG, "unroll: begin: NULL first, h0 or c0 in bank %d", k);
+      if (d->core && (!b.core_h0 || !b.core_c0))
+        return fail(AAA_E_ARG, "unroll: begin: core = 256 needs core_h0 and core_c0 in bank %d", k);
+    }
+  }
+  if (!aligned16(io->pos)) return fail(AAA_E_ALIGN, "unroll: %s: pos must be 16-byte aligned", who);
+  // the state pointers are checked by both calls (NULL is aligned): a recorder that begin would refuse is refused at once
+  bool ok = aligned16(io->h) && aligned16(io->c) && aligned16(io->core_h) && aligned16(io->core_c);
+  for (int k = 0; k < 2; ++k) {
+    const aaa_unroll_bank& b = io->bank[k];
+    ok = ok && aligned16(b.h0) && aligned16(b.c0) && aligned16(b.core_h0) && aligned16(b.core_c0);
+  }
+  if (!ok)
+    return fail(AAA_E_ALIGN, "unroll: %s: h, c, core_h, core_c and the banks' h0, c0, core_h0, core_c0 must be 16-byte "
+                             "aligned", who);
+  if (d->frame_bytes % 16 == 0 && (!aligned16(io->frame) || !aligned16(io->bank[0].frames) || !aligned16(io->bank[1].frames)))
+    return fail(AAA_E_ALIGN, "unroll: %s: frame and the banks' frames must be 16-byte aligned when frame_bytes %% 16 == 0",
+                who);
+  return AAA_OK;
+}
+
+int aaa_unroll_begin(const aaa_unroll_desc* d, const aaa_unroll_io* io, hipStream_t stream) {
+  int r = unroll_check(false, d, io);
+  if (r) return r;
+  if ((r = check_device())) return r;
+  HIPCHK(unroll_begin_launch(*d, *io, stream));
+  return AAA_OK;
+}
+
+int aaa_unroll_record(const aaa_unroll_desc* d, const aaa_unroll_io* io, hipStream_t stream) {
+  int r = unroll_check(true, d, io);
+  if (r) return r;
+  if ((r = check_device())) return r;
+  HIPCHK(unroll_record_launch(*d, *io, stream));
+  return AAA_OK;
+}
+
 // ---- actor step (include/aaa.h; csrc/actor.hip) ----
 // Workspace: conv2 output X (B,P,64), h_t Hs (B,P,128), hid1 (B,512), AO (B,256), LH (B,256),
 // the ConvLSTM's split-K partial tiles, the tile and readout counters, the attention logits,

@@ -7,6 +7,9 @@ train_step(): step() followed by the fused Adam update of the flat params
 step() takes its loss cotangents from outside; step_vtrace() /
 train_step_vtrace() compute them on the device between the forward and the
 backward (V-trace actor-critic, vtrace.py) and share everything else.
+Every step method takes ``initial_state``, the recurrent state before step 0
+as the actors recorded it (unroll.py), and train_on() runs a whole recorded
+unroll; without it an unroll starts from ``reset()``.
 Weights live in one flat fp32 buffer in state_dict order, grads likewise, so
 a bucket is a contiguous slice and no flatten/unflatten copies are needed.
 
@@ -59,7 +62,8 @@ class Learner:
     def __init__(self, B: int, T: int, H: int = 84, W: int = 84, nq: int = 4, A: int = 18,
                  dtype: str = "fp32", device=None, seed: int = 0, group=None, lr: float = 1e-3,
                  frames_u8: bool = False, max_grad_norm: float | None = None, optimizer: str = "adam",
-                 rmsprop: dict | None = None, lr_anneal_steps: int = 0, lr_end: float = 0.0):
+                 rmsprop: dict | None = None, lr_anneal_steps: int = 0, lr_end: float = 0.0,
+                 stateful_core: bool = False):
         if optimizer not in ("adam", "rmsprop"):
             raise ValueError(f"Learner: optimizer must be 'adam' or 'rmsprop' (got {optimizer!r})")
         if optimizer == "adam" and lr_anneal_steps:
@@ -71,7 +75,8 @@ class Learner:
         if unknown:
             raise ValueError(f"Learner: unknown rmsprop setting(s) {sorted(unknown)}; known: "
                              f"{sorted(self.RMSPROP_DEFAULTS)}")
-        self.runner = r = UnrollRunner(B, T, H, W, nq, A, dtype, device, frames_u8=frames_u8, defer_stranded=True)
+        self.runner = r = UnrollRunner(B, T, H, W, nq, A, dtype, device, stateful_core=stateful_core,
+                                       frames_u8=frames_u8, defer_stranded=True)
         self.device = r.device
         params = detinit.deterministic_params(seed, A, nq)
         self.flat = torch.from_numpy(np.concatenate([v.reshape(-1) for v in params.values()])).to(self.device)
@@ -123,16 +128,22 @@ class Learner:
             dist.broadcast(self.flat, src=0, group=group)
             self.comm = torch.cuda.Stream(self.device)   # the gradient all-reduces (RCCL) run here
 
-    def step(self, frames, dlogits, dvalues, overlap: bool = True, comm_timing: bool = False, reset=None):
+    def step(self, frames, dlogits, dvalues, overlap: bool = True, comm_timing: bool = False, reset=None,
+             initial_state=None):
         """One learner iteration; returns (logits, values).  With N > 1 ranks the
         gradients are SUM-all-reduced over RCCL on a side stream, issued after
         the CORE and VISION phases (``schedule``): the HEAD+CORE reduction
         overlaps the vision backward and never runs beside a frame-resident
         launch.  ``comm_timing`` records per-bucket events; read them with
         comm_stats() after a sync.  ``reset``: None, or a (T, B) episode-start
-        mask on the device (``UnrollRunner.forward``; fp32 learners)."""
+        mask on the device (``UnrollRunner.forward``; fp32 learners).
+        ``initial_state``: None (the unroll starts from ``reset()``), or the
+        state before step 0 as the actor held it -- ``(h0, c0)`` (B, h, w, 128),
+        with a stateful core ``(h0, c0, core_h0, core_c0)``, the last two
+        (B, 256) (``Unroll.initial_state``, unroll.py).  Rows with ``reset[0]``
+        start from ``reset()`` whatever it holds (include/aaa.h)."""
         reset = self._reset_mask(reset, None, None)
-        logits, values = self._forward(frames, reset)
+        logits, values = self._forward(frames, reset, initial_state)
         self._backward(frames, dlogits, dvalues, overlap, comm_timing, reset)
         return logits, values
 
@@ -164,7 +175,8 @@ class Learner:
         return reset.contiguous()
 
     def step_vtrace(self, frames, actions, rewards, behaviour_logp=None, done=None, bootstrap=None,
-                    overlap: bool = True, comm_timing: bool = False, reset=None, first=None, **hparams):
+                    overlap: bool = True, comm_timing: bool = False, reset=None, first=None, initial_state=None,
+                    **hparams):
         """One learner iteration on the V-trace actor-critic loss (vtrace.py;
         include/aaa.h ``aaa_vtrace``): pack -> forward -> the loss kernel, from
         this step's own logits / values into the learner's cotangent buffers ->
@@ -184,7 +196,9 @@ class Learner:
         (T, B) episode-start mask, or ``"done"`` = ``episode_starts(done,
         first)``: the step after a ``done`` enters from ``reset()``, and
         ``first`` (B) says which rows start an episode at step 0.  fp32
-        learners (include/aaa.h ``aaa_forward_resets``).
+        learners (include/aaa.h ``aaa_forward_resets``).  ``initial_state``:
+        as in step() -- the state the actor held before step 0, so that the
+        recomputed log pi is the one ``behaviour_logp`` was drawn under.
 
         Nothing in the iteration reads the device from the host: there is no
         ``.item()`` and, unlike ``vtrace_loss``, no validation of the action
@@ -217,7 +231,7 @@ class Learner:
         actions, rewards = dev(actions, torch.int32, tb), dev(rewards, torch.float32, tb)
         behaviour_logp, done = dev(behaviour_logp, torch.float32, tb), dev(done, torch.float32, tb)
         reset = self._reset_mask(reset, done, first)
-        logits, values = self._forward(frames, reset)
+        logits, values = self._forward(frames, reset, initial_state)
         if last:
             bootstrap = values[T - 1, :, int(hparams.get("value_col", 0))].contiguous()
             dl[n:].zero_()
@@ -230,11 +244,20 @@ class Learner:
         self._backward(frames, dl, dv, overlap, comm_timing, reset)
         return logits, values, parts
 
-    def _forward(self, frames, reset=None):
+    def _forward(self, frames, reset=None, initial_state=None):
         r = self.runner
+        h0 = c0 = core = None
+        if initial_state is not None:
+            want = 4 if r.stateful_core else 2
+            if len(initial_state) != want:
+                raise ValueError(f"initial_state must be (h0, c0{', core_h0, core_c0' if want == 4 else ''}) for this "
+                                 f"learner, got {len(initial_state)} tensors")
+            h0, c0 = initial_state[:2]
+            core = tuple(initial_state[2:]) if want == 4 else None
         r.pack(self.flat, self.packed)
-        logits, values, _, _, _ = r.forward(self.flat, self.packed, self.basis, frames, self.ws, want_attn=False,
-                                            reset=reset)
+        # (a stateful-core runner also returns the core's final state: seven values)
+        logits, values = r.forward(self.flat, self.packed, self.basis, frames, self.ws, h0=h0, c0=c0, want_attn=False,
+                                   core=core, reset=reset)[:2]
         return logits, values
 
     def _backward(self, frames, dlogits, dvalues, overlap, comm_timing, reset=None):
@@ -359,16 +382,30 @@ class Learner:
         norm, coef, bad, mx = self.grad_stats.tolist()
         return {"norm": norm, "coef": coef, "nonfinite": int(bad), "max_norm": mx}
 
-    def train_step(self, frames, dlogits, dvalues, overlap: bool = True, reset=None):
-        out = self.step(frames, dlogits, dvalues, overlap=overlap, reset=reset)
+    def train_step(self, frames, dlogits, dvalues, overlap: bool = True, reset=None, initial_state=None):
+        out = self.step(frames, dlogits, dvalues, overlap=overlap, reset=reset, initial_state=initial_state)
         self.optimizer_step()
         return out
 
     def train_step_vtrace(self, frames, actions, rewards, behaviour_logp=None, done=None, bootstrap=None,
-                          overlap: bool = True, reset=None, first=None, **hparams):
+                          overlap: bool = True, reset=None, first=None, initial_state=None, **hparams):
         """step_vtrace() followed by the fused Adam update: a complete learner
         iteration, stream-ordered, with no host round trip."""
         out = self.step_vtrace(frames, actions, rewards, behaviour_logp, done, bootstrap, overlap=overlap,
-                               reset=reset, first=first, **hparams)
+                               reset=reset, first=first, initial_state=initial_state, **hparams)
         self.optimizer_step()
         return out
+
+    def train_on(self, unroll, **hparams):
+        """One complete iteration on an unroll the actors recorded
+        (``UnrollCollector.take()``, unroll.py): train_step_vtrace() on its
+        buffers with ``bootstrap="last"``, from the state the actors held before
+        its step 0.  fp32 learners also cut the state at the episode ends inside
+        it (``reset="done"`` with the unroll's ``first``); bf16 learners refuse a
+        reset mask and get the initial state alone (its rows of ``first`` hold
+        the reset() state already: the recorder stores the state after the
+        episode-start reset)."""
+        if self.runner.dtype == "fp32":
+            hparams = dict(hparams, reset="done", first=unroll.first)
+        return self.train_step_vtrace(unroll.frames, unroll.actions, unroll.rewards, unroll.logp, unroll.done,
+                                      bootstrap="last", initial_state=unroll.initial_state, **hparams)

@@ -193,9 +193,17 @@ class GraphActor:
     stateful policy core; fp32 agents, B <= 16) or the learner's T=1 forward
     (``aaa_forward`` + ``aaa_sample_actions``: bf16 agents, larger B or grids);
     None picks the chain whenever it applies.
+
+    ``recorder`` (``UnrollCollector.rows(b0, B)``, unroll.py) adds two calls
+    to the captured step -- ``aaa_unroll_begin`` before it, ``aaa_unroll_record``
+    after it, on either path -- that reset the rows whose episode ended and
+    write the step into the collector's time-major unroll buffers at a
+    device-side cursor; ``step`` then also takes the reward and done flag that
+    came with the observation.  Without one the captured launches are the
+    step's alone.
     """
 
-    def __init__(self, agent, H: int, W: int, B: int = 1, seed: int = 0, chain: bool | None = None):
+    def __init__(self, agent, H: int, W: int, B: int = 1, seed: int = 0, chain: bool | None = None, recorder=None):
         from .runtime import ActorRunner, UnrollRunner
         self.agent = agent
         dev = next(agent.parameters()).device
@@ -242,6 +250,13 @@ class GraphActor:
         self._host = [(torch.empty(B, H, W, 3, dtype=torch.uint8, pin_memory=True), torch.cuda.Event())
                       for _ in range(4)]
         self._slot = 0
+        self.recorder = recorder
+        if recorder is not None:   # the unroll recorder's two calls ride in the captured step (unroll.py)
+            if recorder.n != B:
+                raise ValueError(f"GraphActor: the recorder holds {recorder.n} rows, the actor steps {B}")
+            recorder.attach(self.frame_u8, self.h, self.c, self.core_h, self.core_c)
+            # reward / done staging beside the frame ring: (pinned (2, B) fp32, its numpy view)
+            self._host_rd = [(t, t.numpy()) for t in (torch.zeros(2, B, pin_memory=True) for _ in self._host)]
         self._refresh()
         stream = torch.cuda.Stream(dev)
         stream.wait_stream(torch.cuda.current_stream(dev))
@@ -253,15 +268,22 @@ class GraphActor:
                 self._outs = self._body()
         torch.cuda.current_stream(dev).wait_stream(stream)
         self.sampler.counter.zero_()   # the warm-up draws do not count: step k uses draw index k
+        if recorder is not None:
+            recorder.restart()         # nor do the warm-up steps it recorded: the cursor starts at zero
         self.reset()
 
     def _body(self):
         r = self.runner
+        rec = self.recorder
+        if rec is not None:
+            rec.begin()
         if self.chain:
             s = self.sampler
             r.step(self.flat, self.packed, self.S, self.frame_u8, self._ws, self.h, self.c, self._logits,
                    self._values, attn=self._attn, seed=s.seed, counter=s.counter, actions=self._actions,
                    logp=self._logp, core_h=self.core_h, core_c=self.core_c)
+            if rec is not None:
+                rec.record(self._actions, self._logp)
             return self._actions, self._logp, self._logits, self._values, self._attn
         X = self.frame_u8                  # uint8, cast in-kernel (AAA_FLAG_FRAMES_U8)
         ws = r.new_workspace()
@@ -274,6 +296,8 @@ class GraphActor:
         if self.stateful:
             self.core_h.copy_(out[5])
             self.core_c.copy_(out[6])
+        if rec is not None:
+            rec.record(action, logp)
         return action, logp, logits[0], values[0], attn[0]
 
     def _refresh(self):
@@ -290,6 +314,8 @@ class GraphActor:
         if self.stateful:
             self.core_h.zero_()
             self.core_c.zero_()
+        if self.recorder is not None:   # the next step starts an episode in every row
+            self.recorder.episode_start()
 
     @property
     def logits(self):
@@ -307,18 +333,58 @@ class GraphActor:
     def attention(self):
         return self._outs[4]
 
-    def step(self, observation):
-        """observation: uint8 (H, W, 3) / (B, H, W, 3) numpy array or tensor."""
+    def step(self, observation, reward=None, done=None):
+        """observation: uint8 (H, W, 3) / (B, H, W, 3) numpy array or tensor.
+
+        With a recorder, ``reward`` and ``done`` (B,) are what the environment
+        returned WITH this observation -- the result of the previous step's
+        action; ``done[b] != 0`` says row b's observation is the first of a new
+        episode.  None is zeros.  On the first step after ``reset()`` every row
+        starts an episode whatever ``done`` says."""
         self._refresh()
-        if isinstance(observation, torch.Tensor) and observation.is_cuda:
+        rec = self.recorder
+        if rec is None and (reward is not None or done is not None):
+            raise ValueError("GraphActor.step: reward / done belong to an actor with a recorder")
+        if rec is not None and rec.fresh:
+            done = None   # reset() / restart() have set done_in = 1
+        on_dev = [isinstance(x, torch.Tensor) and x.is_cuda for x in (observation, reward, done)]
+        ring = not on_dev[0] or (reward is not None and not on_dev[1]) or (done is not None and not on_dev[2])
+        if ring:
+            slot = self._slot
+            buf, copied = self._host[slot]
+            self._slot = (slot + 1) % len(self._host)
+            copied.synchronize()   # the H2D copies that read this slot's buffers 4 steps ago have run
+        if on_dev[0]:
             self.frame_u8.view(self.B, self.H, self.W, 3).copy_(observation.reshape(self.B, self.H, self.W, 3))
         else:
             src = torch.as_tensor(np.ascontiguousarray(observation)).reshape(self.B, self.H, self.W, 3)
-            buf, done = self._host[self._slot]
-            self._slot = (self._slot + 1) % len(self._host)
-            done.synchronize()   # the H2D copy that read this buffer 4 steps ago has run
             buf.copy_(src)
             self.frame_u8.view(self.B, self.H, self.W, 3).copy_(buf, non_blocking=True)
-            done.record(torch.cuda.current_stream(self.device))
+        if rec is not None:
+            given = ((reward, rec.reward_in), (done, rec.done_in))
+            if all(x is not None and not on_dev[1 + i] for i, (x, _) in enumerate(given)):
+                stage, stage_np = self._host_rd[slot]   # both from the host, the usual case: one upload
+                stage_np[0], stage_np[1] = np.asarray(reward).reshape(self.B), np.asarray(done).reshape(self.B)
+                rec.rd_in.copy_(stage, non_blocking=True)
+                rec.clear = [False, False]
+                given = ()
+            for i, (x, dst) in enumerate(given):
+                if x is None:   # zeros: written once, then known to be there
+                    if not rec.clear[i] and not (i == 1 and rec.fresh):
+                        dst.zero_()
+                        rec.clear[i] = True
+                    continue
+                rec.clear[i] = False
+                if on_dev[1 + i]:
+                    dst.copy_(x.reshape(self.B))
+                else:
+                    stage, stage_np = self._host_rd[slot]
+                    stage_np[i] = np.asarray(x).reshape(self.B)
+                    dst.copy_(stage[i], non_blocking=True)
+            rec.fresh = False
+        if ring:
+            copied.record(torch.cuda.current_stream(self.device))
         self.graph.replay()
+        if rec is not None:
+            rec.steps += 1
         return self._outs[0]
