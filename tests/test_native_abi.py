@@ -202,6 +202,19 @@ def test_adam_counted_rejects_null_counter():
     assert lib.aaa_adam_step_counted(ctypes.byref(hp), None, None, 0, None, None, None, None, None, None, None) == -1
 
 
+def test_adam_refuses_too_large_tensor_before_the_device():
+    """A tensor whose chunks exceed the 2^30 a grid may hold is refused with AAA_E_ARG like every
+    other argument, so also on a machine with no device (dummy aligned addresses, never dereferenced)."""
+    lib = N.load()
+    hp = N.AdamHP(1e-3, 0.9, 0.999, 1e-8, 0.0, 0, 0)
+    two = (ctypes.c_void_p * 2)(4096, 4096 + 64)
+    for numel, t in (((1 << 43, 7), b"tensor 0"), ((5, 1 << 43), b"tensor 1"), ((1 << 42, 1 << 42), b"tensor 1")):
+        rc = lib.aaa_adam_step_counted(ctypes.byref(hp), 4096, None, 2, two, two, two, two, None,
+                                       (ctypes.c_size_t * 2)(*numel), None)
+        msg = lib.aaa_last_error()
+        assert rc == -1 and msg.startswith(b"adam") and b"too large" in msg and t in msg, (rc, msg)
+
+
 @pytest.mark.parametrize("what,nq,o_ld,q_stride,sq,word", [
     ("o_ld below the 136 the 16-byte loads need", 4, 128, 0, None, b"o_ld"),
     ("o_ld not a multiple of 8", 4, 140, 0, None, b"o_ld"),

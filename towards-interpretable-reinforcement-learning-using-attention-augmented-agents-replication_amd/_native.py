@@ -377,11 +377,15 @@ def unroll_record(desc: UnrollDesc, io: UnrollIO, stream=None) -> None:
     check(load().aaa_unroll_record(ctypes.byref(desc), ctypes.byref(io), st), "unroll_record")
 
 
-def _tensor_table(ts):
-    """(n, host array of the device pointers, host array of the element counts) of a tensor list."""
+def _tensor_table(ts, *more):
+    """(n, host array of the element counts of the tensor list ``ts``, host array of its device
+    pointers, and one such array -- or None, a NULL argument -- for each further list or None)."""
     n = len(ts)
-    return (n, (ctypes.c_void_p * max(n, 1))(*[t.data_ptr() for t in ts]),
-            (ctypes.c_size_t * max(n, 1))(*[t.numel() for t in ts]))
+    VP = ctypes.c_void_p * max(n, 1)
+    for group in more:
+        assert group is None or len(group) == n
+    return (n, (ctypes.c_size_t * max(n, 1))(*[t.numel() for t in ts]),
+            *[None if group is None else VP(*[t.data_ptr() for t in group]) for group in (ts,) + more])
 
 
 def grad_norm_scratch_bytes(numels) -> int:
@@ -395,7 +399,7 @@ def grad_norm(max_norm: float, grads, stats, scratch, stream=None) -> None:
     coefficient for ``max_norm`` into ``stats`` (4 fp32 device elements: norm,
     coefficient, non-finite flag, max_norm; include/aaa.h aaa_grad_norm).
     ``scratch``: a device tensor of at least grad_norm_scratch_bytes() bytes.  No host sync."""
-    n, gp, numel = _tensor_table(grads)
+    n, numel, gp = _tensor_table(grads)
     need = load().aaa_grad_norm_scratch_bytes(n, numel)
     if scratch.numel() * scratch.element_size() < need:
         raise ValueError(f"grad_norm: scratch holds {scratch.numel() * scratch.element_size()} bytes, needs {need}")
@@ -407,7 +411,7 @@ def grad_norm(max_norm: float, grads, stats, scratch, stream=None) -> None:
 
 def grad_scale(stats, grads, stream=None) -> None:
     """Enqueue ``g *= stats[1]`` in place over the fp32 device tensors ``grads`` (aaa_grad_scale)."""
-    n, gp, numel = _tensor_table(grads)
+    n, numel, gp = _tensor_table(grads)
     st = stream if stream is not None else stream_ptr(stats.device)
     check(load().aaa_grad_scale(stats.data_ptr(), n, gp, numel, st), "grad_scale")
 
@@ -424,33 +428,22 @@ def adam_step(hp: AdamHP, step: int, params, grads, exp_avg, exp_avg_sq, max_exp
     clip[1], skipped when clip[2] != 0 -- it needs ``step_dev``)."""
     if clip is not None and step_dev is None:
         raise ValueError("adam_step: clip= needs step_dev (aaa_adam_step_clipped is the counted update)")
-    n = len(params)
-    VP = ctypes.c_void_p * max(n, 1)
-    def arr(ts):
-        return VP(*[t.data_ptr() for t in ts]) if ts is not None else None
-    numel = (ctypes.c_size_t * max(n, 1))(*[t.numel() for t in params])
-    for group in (grads, exp_avg, exp_avg_sq) + ((max_exp_avg_sq,) if max_exp_avg_sq is not None else ()):
-        assert len(group) == n
-    mx = arr(max_exp_avg_sq)
+    n, numel, *arrays = _tensor_table(params, grads, exp_avg, exp_avg_sq, max_exp_avg_sq)
     st = stream if stream is not None else stream_ptr()
+    gd = guard.data_ptr() if guard is not None else None
     if step_dev is not None:
         assert step_dev.numel() == 1 and step_dev.is_cuda and str(step_dev.dtype) == "torch.int32"
     if clip is not None:
-        check(load().aaa_adam_step_clipped(ctypes.byref(hp), step_dev.data_ptr(),
-                                           guard.data_ptr() if guard is not None else None, clip.data_ptr(), n,
-                                           arr(params), arr(grads), arr(exp_avg), arr(exp_avg_sq), mx, numel, st),
-              "adam_step_clipped")
+        check(load().aaa_adam_step_clipped(ctypes.byref(hp), step_dev.data_ptr(), gd, clip.data_ptr(), n, *arrays,
+                                           numel, st), "adam_step_clipped")
     elif step_dev is not None:
-        check(load().aaa_adam_step_counted(ctypes.byref(hp), step_dev.data_ptr(),
-                                           guard.data_ptr() if guard is not None else None, n, arr(params),
-                                           arr(grads), arr(exp_avg), arr(exp_avg_sq), mx, numel, st),
+        check(load().aaa_adam_step_counted(ctypes.byref(hp), step_dev.data_ptr(), gd, n, *arrays, numel, st),
               "adam_step_counted")
     elif guard is not None:
-        check(load().aaa_adam_step_guarded(ctypes.byref(hp), int(step), guard.data_ptr(), n, arr(params), arr(grads),
-                                           arr(exp_avg), arr(exp_avg_sq), mx, numel, st), "adam_step_guarded")
+        check(load().aaa_adam_step_guarded(ctypes.byref(hp), int(step), gd, n, *arrays, numel, st),
+              "adam_step_guarded")
     else:
-        check(load().aaa_adam_step(ctypes.byref(hp), int(step), n, arr(params), arr(grads), arr(exp_avg),
-                                   arr(exp_avg_sq), mx, numel, st), "adam_step")
+        check(load().aaa_adam_step(ctypes.byref(hp), int(step), n, *arrays, numel, st), "adam_step")
 
 
 def rmsprop_step(hp: RmspropHP, step: int, params, grads, square_avg, momentum_buf=None, grad_avg=None, stream=None,
@@ -463,20 +456,13 @@ def rmsprop_step(hp: RmspropHP, step: int, params, grads, square_avg, momentum_b
     updates applied so far from it, and it advances on the device only when
     the update was applied; ``clip``, grad_norm()'s stats tensor: the update
     runs on grad * clip[1] and is skipped when clip[2] != 0."""
-    n = len(params)
-    VP = ctypes.c_void_p * max(n, 1)
-    def arr(ts):
-        return VP(*[t.data_ptr() for t in ts]) if ts is not None else None
+    n, numel, *arrays = _tensor_table(params, grads, square_avg, momentum_buf, grad_avg)
     def one(t):
         return t.data_ptr() if t is not None else None
-    numel = (ctypes.c_size_t * max(n, 1))(*[t.numel() for t in params])
-    for group in (grads, square_avg, momentum_buf, grad_avg):
-        assert group is None or len(group) == n
     if step_dev is not None:
         assert step_dev.numel() == 1 and step_dev.is_cuda and str(step_dev.dtype) == "torch.int32"
     if clip is not None and (clip.numel() < 4 or str(clip.dtype) != "torch.float32"):
         raise ValueError("rmsprop_step: clip must hold grad_norm()'s 4 fp32 elements")
     st = stream if stream is not None else stream_ptr()
-    check(load().aaa_rmsprop_step(ctypes.byref(hp), int(step), one(step_dev), one(guard), one(clip), n, arr(params),
-                                  arr(grads), arr(square_avg), arr(momentum_buf), arr(grad_avg), numel, st),
-          "rmsprop_step")
+    check(load().aaa_rmsprop_step(ctypes.byref(hp), int(step), one(step_dev), one(guard), one(clip), n, *arrays,
+                                  numel, st), "rmsprop_step")

@@ -6,17 +6,22 @@ namespace aaa {
 
 constexpr int kAdamMaxTensors = 48;   // per launch (kernel-argument table)
 
-struct AdamTable {
-  float* p[kAdamMaxTensors];
-  const float* g[kAdamMaxTensors];
-  float* m[kAdamMaxTensors];
-  float* v[kAdamMaxTensors];
-  float* vmax[kAdamMaxTensors];
+// The kernel-argument table of every multi-tensor kernel (optim.hip chunk_walk): K device
+// streams per tensor, all nullptr for a stream the launch does not use.  K = 5 for Adam and
+// RMSProp, 1 for the gradient kernels (aaa_grad_norm / aaa_grad_scale).
+template <int K>
+struct TensorTable {
+  float* s[K][kAdamMaxTensors];
   size_t numel[kAdamMaxTensors];
   int chunk0[kAdamMaxTensors];        // first workgroup of each tensor
-  unsigned char vec[kAdamMaxTensors]; // all four pointers 16-byte aligned
+  unsigned char vec[kAdamMaxTensors]; // every stream in use 16-byte aligned
   int n;
 };
+
+// A table's streams, in the order of the C entries' arrays.
+enum { kParam = 0, kGrad = 1, kExpAvg = 2, kExpAvgSq = 3, kMaxExpAvgSq = 4,   // Adam
+       kSquareAvg = 2, kMomentumBuf = 3, kGradAvg = 4,                        // RMSProp (the last two when used)
+       kGradOnly = 0 };                                                       // K = 1 (read-only for the norm)
 
 struct AdamHost {
   double lr, beta1, beta2, eps, weight_decay;
@@ -29,28 +34,6 @@ struct AdamHost {
                                   // no update (nor count) when stats[2] != 0
 };
 
-// aaa_grad_norm / aaa_grad_scale: the gradients alone, chunked as AdamTable is
-struct GradTable {
-  float* g[kAdamMaxTensors];          // read-only for the norm
-  size_t numel[kAdamMaxTensors];
-  int chunk0[kAdamMaxTensors];
-  unsigned char vec[kAdamMaxTensors]; // pointer 16-byte aligned
-  int n;
-};
-
-// aaa_rmsprop_step: chunked as AdamTable is; b (momentum buffer) and a (grad_avg) are nullptr when unused
-struct RmspropTable {
-  float* p[kAdamMaxTensors];
-  const float* g[kAdamMaxTensors];
-  float* v[kAdamMaxTensors];
-  float* b[kAdamMaxTensors];
-  float* a[kAdamMaxTensors];
-  size_t numel[kAdamMaxTensors];
-  int chunk0[kAdamMaxTensors];
-  unsigned char vec[kAdamMaxTensors]; // every pointer in use 16-byte aligned
-  int n;
-};
-
 struct RmspropHost {
   double lr, alpha, eps, weight_decay, momentum, lr_end;
   long anneal_steps;              // 0: constant lr
@@ -61,15 +44,15 @@ struct RmspropHost {
   const float* stats = nullptr;   // aaa_grad_norm's stats: g = grad * stats[1], no update (nor count) when stats[2] != 0
 };
 
-int adam_chunks(size_t numel);
+long adam_chunks(size_t numel);   // workgroups of one tensor; long, so a caller can refuse a count no grid holds
 // advance: count this update on h.step_dev after the launch (the last table of a step)
-hipError_t rmsprop_launch(const RmspropTable& tab, int nchunks, const RmspropHost& h, hipStream_t st, bool advance);
+hipError_t rmsprop_launch(const TensorTable<5>& tab, int nchunks, const RmspropHost& h, hipStream_t st, bool advance);
 // advance: count this update on h.step_dev after the launch (the last table of a step)
-hipError_t adam_launch(const AdamTable& tab, int nchunks, const AdamHost& h, hipStream_t st, bool advance);
+hipError_t adam_launch(const TensorTable<5>& tab, int nchunks, const AdamHost& h, hipStream_t st, bool advance);
 // one double per workgroup to scratch[chunk_base + workgroup]; then one workgroup over all nchunks partials
-hipError_t gradsq_launch(const GradTable& tab, int nchunks, int chunk_base, double* scratch, hipStream_t st);
+hipError_t gradsq_launch(const TensorTable<1>& tab, int nchunks, int chunk_base, double* scratch, hipStream_t st);
 hipError_t gradsq_finish_launch(const double* scratch, int nchunks, double max_norm, float* stats, hipStream_t st);
-hipError_t grad_scale_launch(const GradTable& tab, int nchunks, const float* stats, hipStream_t st);
+hipError_t grad_scale_launch(const TensorTable<1>& tab, int nchunks, const float* stats, hipStream_t st);
 hipError_t pair_flag_launch(const int* report, int* base, float* dst, hipStream_t st);
 
 // loss.hip: REINFORCE (finish_episode) loss + logits cotangent, one workgroup per episode

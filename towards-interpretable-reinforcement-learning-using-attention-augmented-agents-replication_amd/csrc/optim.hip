@@ -57,32 +57,96 @@ constexpr int kAdamThreads = 256;
 constexpr int kAdamVec = 4;                                   // floats per 16-byte access
 constexpr int kAdamChunk = kAdamThreads * kAdamVec * 4;       // elements per workgroup
 
-// One workgroup's chunk of one tensor.  kScale: the gradient is grad * coef,
-// rounded to fp32 before anything else reads it (grad.mul_(coef)): __fmul_rn
-// keeps the product out of a contraction with adam_elem's first add.
-template <bool kScale>
-__device__ __forceinline__ void adam_chunk(const AdamTable& tab, const AdamScalars& s, float coef) {
+// The chunk walk of every multi-tensor kernel here.  Workgroup -> (tensor,
+// chunk) through the chunk prefix table, then the chunk's elements in a fixed
+// order (k_gradsq's per-thread sum is defined by it): a tensor whose streams
+// are all 16-byte aligned in 4 rounds of 16-byte accesses, a vector short of
+// the end element by element by the same thread; any other tensor in 16
+// scalar rounds.  vec4(S, i): the caller's work on elements [i, i + 4) of
+// the tensor's streams S; one(S, j): the same on element j.
+template <int K, class Vec4, class One>
+__device__ __forceinline__ void chunk_walk(const TensorTable<K>& tab, Vec4&& vec4, One&& one) {
   const int b = blockIdx.x;
   int t = 0;
   while (t + 1 < tab.n && tab.chunk0[t + 1] <= b) ++t;
   const size_t n = tab.numel[t];
   const size_t base = (size_t)(b - tab.chunk0[t]) * kAdamChunk;
-  float* __restrict__ P = tab.p[t];
-  const float* __restrict__ G = tab.g[t];
-  float* __restrict__ M = tab.m[t];
-  float* __restrict__ V = tab.v[t];
-  float* __restrict__ X = tab.vmax[t];
-  const bool vec = tab.vec[t];
-  auto grad = [&](float g) { return kScale ? __fmul_rn(g, coef) : g; };
-  if (vec) {
+  float* S[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) S[k] = tab.s[k][t];
+  if (tab.vec[t]) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const size_t i = base + ((size_t)r * kAdamThreads + threadIdx.x) * kAdamVec;
       if (i + kAdamVec <= n) {
-        f32x4 p = *reinterpret_cast<const f32x4*>(P + i);
-        const f32x4 g = *reinterpret_cast<const f32x4*>(G + i);
-        f32x4 m = *reinterpret_cast<const f32x4*>(M + i);
-        f32x4 v = *reinterpret_cast<const f32x4*>(V + i);
+        vec4(S, i);
+      } else {
+        for (size_t j = i; j < n; ++j) one(S, j);
+      }
+    }
+  } else {
+    for (int r = 0; r < kAdamVec * 4; ++r) {
+      const size_t j = base + (size_t)r * kAdamThreads + threadIdx.x;
+      if (j < n) one(S, j);
+    }
+  }
+}
+
+// The walk for a body stated once, elem(x) on one element's values x[K].
+// kLoad / kStore: the streams read into x before it and written back after
+// it, one bit per stream; a stream not loaded is 0 in x and never touched.
+template <unsigned kLoad, unsigned kStore, int K, class Elem>
+__device__ __forceinline__ void chunk_walk_elem(const TensorTable<K>& tab, Elem&& elem) {
+  chunk_walk(
+      tab,
+      [&](float* const (&S)[K], size_t i) {
+        f32x4 v[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+          v[k] = (kLoad >> k & 1) ? *reinterpret_cast<const f32x4*>(S[k] + i) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float x[K];
+#pragma unroll
+          for (int k = 0; k < K; ++k) x[k] = v[k][e];
+          elem(x);
+#pragma unroll
+          for (int k = 0; k < K; ++k) v[k][e] = x[k];
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+          if (kStore >> k & 1) *reinterpret_cast<f32x4*>(S[k] + i) = v[k];
+      },
+      [&](float* const (&S)[K], size_t j) {
+        float x[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) x[k] = (kLoad >> k & 1) ? S[k][j] : 0.f;
+        elem(x);
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+          if (kStore >> k & 1) S[k][j] = x[k];
+      });
+}
+
+constexpr unsigned stream_bit(int k) { return 1u << k; }
+
+// One workgroup's chunk of one tensor.  kScale: the gradient is grad * coef,
+// rounded to fp32 before anything else reads it (grad.mul_(coef)): __fmul_rn
+// keeps the product out of a contraction with adam_elem's first add.
+// max_exp_avg_sq is there or not at run time, so Adam gives the walk its own
+// two forms; which multiply of adam_elem fuses with which add follows from
+// how the compiler packs exactly these forms, so they stay as they are.
+template <bool kScale>
+__device__ __forceinline__ void adam_chunk(const TensorTable<5>& tab, const AdamScalars& s, float coef) {
+  auto grad = [&](float g) { return kScale ? __fmul_rn(g, coef) : g; };
+  chunk_walk(
+      tab,
+      [&](float* const (&S)[5], size_t i) {
+        float* X = S[kMaxExpAvgSq];
+        f32x4 p = *reinterpret_cast<const f32x4*>(S[kParam] + i);
+        const f32x4 g = *reinterpret_cast<const f32x4*>(S[kGrad] + i);
+        f32x4 m = *reinterpret_cast<const f32x4*>(S[kExpAvg] + i);
+        f32x4 v = *reinterpret_cast<const f32x4*>(S[kExpAvgSq] + i);
         f32x4 x = X ? *reinterpret_cast<const f32x4*>(X + i) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -90,30 +154,23 @@ __device__ __forceinline__ void adam_chunk(const AdamTable& tab, const AdamScala
           adam_elem(pe, grad(g[e]), me, ve, X ? &xe : nullptr, s);
           p[e] = pe; m[e] = me; v[e] = ve; x[e] = xe;
         }
-        *reinterpret_cast<f32x4*>(P + i) = p;
-        *reinterpret_cast<f32x4*>(M + i) = m;
-        *reinterpret_cast<f32x4*>(V + i) = v;
+        *reinterpret_cast<f32x4*>(S[kParam] + i) = p;
+        *reinterpret_cast<f32x4*>(S[kExpAvg] + i) = m;
+        *reinterpret_cast<f32x4*>(S[kExpAvgSq] + i) = v;
         if (X) *reinterpret_cast<f32x4*>(X + i) = x;
-      } else {
-        for (size_t j = i; j < n; ++j) adam_elem(P[j], grad(G[j]), M[j], V[j], X ? X + j : nullptr, s);
-      }
-    }
-  } else {
-    for (int r = 0; r < kAdamVec * 4; ++r) {
-      const size_t j = base + (size_t)r * kAdamThreads + threadIdx.x;
-      if (j < n) adam_elem(P[j], grad(G[j]), M[j], V[j], X ? X + j : nullptr, s);
-    }
-  }
+      },
+      [&](float* const (&S)[5], size_t j) {
+        float* X = S[kMaxExpAvgSq];
+        adam_elem(S[kParam][j], grad(S[kGrad][j]), S[kExpAvg][j], S[kExpAvgSq][j], X ? X + j : nullptr, s);
+      });
 }
 
-// Workgroup -> (tensor, chunk) through the chunk prefix table; tensors whose
-// pointers are all 16-byte aligned use 16-byte vectors, the rest scalars.
 // kClip (aaa_adam_step_clipped): no update either when the gradient norm was
 // not finite (stats[2]); otherwise the gradient is grad * stats[1].  The
 // coefficient is the same for the whole grid, so a step the clip leaves alone
 // (exactly 1.0f) takes the unscaled path.
 template <bool kClip>
-__global__ void __launch_bounds__(kAdamThreads) k_adam(AdamTable tab, AdamScalars s) {
+__global__ void __launch_bounds__(kAdamThreads) k_adam(TensorTable<5> tab, AdamScalars s) {
   if (s.guard && *s.guard != 0.f) return;   // gradients of a stranded launch: no update on any rank
   float coef = 1.f;
   if (kClip) {
@@ -131,7 +188,7 @@ __global__ void k_adam_advance(const float* __restrict__ guard, const float* __r
   if (threadIdx.x == 0 && !(guard && *guard != 0.f) && !(stats && stats[2] != 0.f)) step_dev[0] = step_dev[0] + 1;
 }
 
-hipError_t adam_launch(const AdamTable& tab, int nchunks, const AdamHost& h, hipStream_t st, bool advance) {
+hipError_t adam_launch(const TensorTable<5>& tab, int nchunks, const AdamHost& h, hipStream_t st, bool advance) {
   AdamScalars s;
   s.wd = (float)h.weight_decay;
   s.one_m_b1 = (float)(1.0 - h.beta1);
@@ -204,62 +261,20 @@ __device__ __forceinline__ void rmsprop_elem(float& p, float g, float& v, float&
   }
 }
 
-// One workgroup's chunk of one tensor; kScale as in adam_chunk.  B is touched only with kMom, A only with kCent.
+// One workgroup's chunk of one tensor; kScale as in adam_chunk.  The momentum buffer is touched only with kMom, grad_avg only with kCent.
 template <bool kScale, bool kMom, bool kCent>
-__device__ __forceinline__ void rmsprop_chunk(const RmspropTable& tab, const RmspropScalars& s, float coef) {
-  const int blk = blockIdx.x;
-  int t = 0;
-  while (t + 1 < tab.n && tab.chunk0[t + 1] <= blk) ++t;
-  const size_t n = tab.numel[t];
-  const size_t base = (size_t)(blk - tab.chunk0[t]) * kAdamChunk;
-  float* __restrict__ P = tab.p[t];
-  const float* __restrict__ G = tab.g[t];
-  float* __restrict__ V = tab.v[t];
-  float* __restrict__ B = tab.b[t];
-  float* __restrict__ A = tab.a[t];
-  auto grad = [&](float g) { return kScale ? __fmul_rn(g, coef) : g; };
-  auto scalar = [&](size_t j) {
-    float be = kMom ? B[j] : 0.f, ae = kCent ? A[j] : 0.f;
-    rmsprop_elem<kMom, kCent>(P[j], grad(G[j]), V[j], be, ae, s);
-    if (kMom) B[j] = be;
-    if (kCent) A[j] = ae;
-  };
-  if (tab.vec[t]) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const size_t i = base + ((size_t)r * kAdamThreads + threadIdx.x) * kAdamVec;
-      if (i + kAdamVec <= n) {
-        const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-        f32x4 p = *reinterpret_cast<const f32x4*>(P + i);
-        const f32x4 g = *reinterpret_cast<const f32x4*>(G + i);
-        f32x4 v = *reinterpret_cast<const f32x4*>(V + i);
-        f32x4 b = kMom ? *reinterpret_cast<const f32x4*>(B + i) : zero;
-        f32x4 a = kCent ? *reinterpret_cast<const f32x4*>(A + i) : zero;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float pe = p[e], ve = v[e], be = b[e], ae = a[e];
-          rmsprop_elem<kMom, kCent>(pe, grad(g[e]), ve, be, ae, s);
-          p[e] = pe; v[e] = ve; b[e] = be; a[e] = ae;
-        }
-        *reinterpret_cast<f32x4*>(P + i) = p;
-        *reinterpret_cast<f32x4*>(V + i) = v;
-        if (kMom) *reinterpret_cast<f32x4*>(B + i) = b;
-        if (kCent) *reinterpret_cast<f32x4*>(A + i) = a;
-      } else {
-        for (size_t j = i; j < n; ++j) scalar(j);
-      }
-    }
-  } else {
-    for (int r = 0; r < kAdamVec * 4; ++r) {
-      const size_t j = base + (size_t)r * kAdamThreads + threadIdx.x;
-      if (j < n) scalar(j);
-    }
-  }
+__device__ __forceinline__ void rmsprop_chunk(const TensorTable<5>& tab, const RmspropScalars& s, float coef) {
+  constexpr unsigned kState = stream_bit(kParam) | stream_bit(kSquareAvg) | (kMom ? stream_bit(kMomentumBuf) : 0u) |
+                              (kCent ? stream_bit(kGradAvg) : 0u);
+  chunk_walk_elem<kState | stream_bit(kGrad), kState>(tab, [&](float (&x)[5]) {
+    rmsprop_elem<kMom, kCent>(x[kParam], kScale ? __fmul_rn(x[kGrad], coef) : x[kGrad], x[kSquareAvg],
+                              x[kMomentumBuf], x[kGradAvg], s);
+  });
 }
 
 // k_adam's skips, in its order: the guard, then (kClip) the norm's flag, both before any load.
 template <bool kClip, bool kMom, bool kCent>
-__global__ void __launch_bounds__(kAdamThreads) k_rmsprop(RmspropTable tab, RmspropScalars s) {
+__global__ void __launch_bounds__(kAdamThreads) k_rmsprop(TensorTable<5> tab, RmspropScalars s) {
   if (s.guard && *s.guard != 0.f) return;
   float coef = 1.f;
   if (kClip) {
@@ -272,12 +287,12 @@ __global__ void __launch_bounds__(kAdamThreads) k_rmsprop(RmspropTable tab, Rmsp
 }
 
 template <bool kClip, bool kMom>
-static void rmsprop_dispatch(bool cent, int nchunks, hipStream_t st, const RmspropTable& tab, const RmspropScalars& s) {
+static void rmsprop_dispatch(bool cent, int nchunks, hipStream_t st, const TensorTable<5>& tab, const RmspropScalars& s) {
   if (cent) hipLaunchKernelGGL((k_rmsprop<kClip, kMom, true>), dim3(nchunks), dim3(kAdamThreads), 0, st, tab, s);
   else hipLaunchKernelGGL((k_rmsprop<kClip, kMom, false>), dim3(nchunks), dim3(kAdamThreads), 0, st, tab, s);
 }
 
-hipError_t rmsprop_launch(const RmspropTable& tab, int nchunks, const RmspropHost& h, hipStream_t st, bool advance) {
+hipError_t rmsprop_launch(const TensorTable<5>& tab, int nchunks, const RmspropHost& h, hipStream_t st, bool advance) {
   RmspropScalars s;
   s.wd = (float)h.weight_decay;
   s.alpha = (float)h.alpha;
@@ -325,35 +340,12 @@ __device__ __forceinline__ double wg_sum_fixed(double v, double* red) {
   return ((red[0] + red[1]) + red[2]) + red[3];
 }
 
-__global__ void __launch_bounds__(kAdamThreads) k_gradsq(GradTable tab, double* __restrict__ scratch, int chunk_base) {
+__global__ void __launch_bounds__(kAdamThreads) k_gradsq(TensorTable<1> tab, double* __restrict__ scratch, int chunk_base) {
   __shared__ double red[kAdamThreads / 64];
-  const int b = blockIdx.x;
-  int t = 0;
-  while (t + 1 < tab.n && tab.chunk0[t + 1] <= b) ++t;
-  const size_t n = tab.numel[t];
-  const size_t base = (size_t)(b - tab.chunk0[t]) * kAdamChunk;
-  const float* __restrict__ G = tab.g[t];
   double acc = 0.0;
-  if (tab.vec[t]) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const size_t i = base + ((size_t)r * kAdamThreads + threadIdx.x) * kAdamVec;
-      if (i + kAdamVec <= n) {
-        const f32x4 g = *reinterpret_cast<const f32x4*>(G + i);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc += (double)g[e] * (double)g[e];
-      } else {
-        for (size_t j = i; j < n; ++j) acc += (double)G[j] * (double)G[j];
-      }
-    }
-  } else {
-    for (int r = 0; r < kAdamVec * 4; ++r) {
-      const size_t j = base + (size_t)r * kAdamThreads + threadIdx.x;
-      if (j < n) acc += (double)G[j] * (double)G[j];
-    }
-  }
+  chunk_walk_elem<stream_bit(kGradOnly), 0u>(tab, [&](float (&x)[1]) { acc += (double)x[0] * (double)x[0]; });
   const double tot = wg_sum_fixed(acc, red);
-  if (threadIdx.x == 0) scratch[(size_t)chunk_base + b] = tot;
+  if (threadIdx.x == 0) scratch[(size_t)chunk_base + blockIdx.x] = tot;
 }
 
 // One workgroup: the partials in a fixed order, then the four stats (include/aaa.h).
@@ -375,7 +367,7 @@ __global__ void __launch_bounds__(kAdamThreads) k_gradsq_finish(const double* __
   }
 }
 
-hipError_t gradsq_launch(const GradTable& tab, int nchunks, int chunk_base, double* scratch, hipStream_t st) {
+hipError_t gradsq_launch(const TensorTable<1>& tab, int nchunks, int chunk_base, double* scratch, hipStream_t st) {
   if (nchunks > 0) hipLaunchKernelGGL(k_gradsq, dim3(nchunks), dim3(kAdamThreads), 0, st, tab, scratch, chunk_base);
   return hipGetLastError();
 }
@@ -386,37 +378,13 @@ hipError_t gradsq_finish_launch(const double* scratch, int nchunks, double max_n
 }
 
 // g *= stats[1] in place; nothing to do (and nothing written) when the clip left the step alone.
-__global__ void __launch_bounds__(kAdamThreads) k_grad_scale(GradTable tab, const float* __restrict__ stats) {
+__global__ void __launch_bounds__(kAdamThreads) k_grad_scale(TensorTable<1> tab, const float* __restrict__ stats) {
   const float coef = stats[1];
   if (coef == 1.f) return;
-  const int b = blockIdx.x;
-  int t = 0;
-  while (t + 1 < tab.n && tab.chunk0[t + 1] <= b) ++t;
-  const size_t n = tab.numel[t];
-  const size_t base = (size_t)(b - tab.chunk0[t]) * kAdamChunk;
-  float* __restrict__ G = tab.g[t];
-  if (tab.vec[t]) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const size_t i = base + ((size_t)r * kAdamThreads + threadIdx.x) * kAdamVec;
-      if (i + kAdamVec <= n) {
-        f32x4 g = *reinterpret_cast<const f32x4*>(G + i);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) g[e] = g[e] * coef;
-        *reinterpret_cast<f32x4*>(G + i) = g;
-      } else {
-        for (size_t j = i; j < n; ++j) G[j] = G[j] * coef;
-      }
-    }
-  } else {
-    for (int r = 0; r < kAdamVec * 4; ++r) {
-      const size_t j = base + (size_t)r * kAdamThreads + threadIdx.x;
-      if (j < n) G[j] = G[j] * coef;
-    }
-  }
+  chunk_walk_elem<stream_bit(kGradOnly), stream_bit(kGradOnly)>(tab, [&](float (&x)[1]) { x[0] = x[0] * coef; });
 }
 
-hipError_t grad_scale_launch(const GradTable& tab, int nchunks, const float* stats, hipStream_t st) {
+hipError_t grad_scale_launch(const TensorTable<1>& tab, int nchunks, const float* stats, hipStream_t st) {
   if (nchunks > 0) hipLaunchKernelGGL(k_grad_scale, dim3(nchunks), dim3(kAdamThreads), 0, st, tab, stats);
   return hipGetLastError();
 }
@@ -438,6 +406,6 @@ hipError_t pair_flag_launch(const int* report, int* base, float* dst, hipStream_
   return hipGetLastError();
 }
 
-int adam_chunks(size_t numel) { return (int)((numel + kAdamChunk - 1) / kAdamChunk); }
+long adam_chunks(size_t numel) { return (long)((numel + kAdamChunk - 1) / kAdamChunk); }
 
 }  // namespace aaa

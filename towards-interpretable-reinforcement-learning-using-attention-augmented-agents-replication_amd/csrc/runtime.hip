@@ -20,6 +20,48 @@
 
 using namespace aaa;
 
+// ---- the multi-tensor entries (Adam, RMSProp, clip; optim.h TensorTable) ----
+// streams[k]: an entry's k-th array of device pointers, nullptr when the call does not use it.
+// The per-tensor refusals, all before the device; who: the entry's message prefix.  The chunks
+// that must fit one grid index are one table's (per_table: Adam, RMSProp) or, for the clip
+// entries, all tensors': there the partial index runs on through the tables.
+template <int K>
+static int check_tensors(const char* who, int ntensors, const float* const* const (&streams)[K], const size_t* numel,
+                         bool per_table) {
+  long nch = 0;
+  for (int t = 0; t < ntensors; ++t) {
+    if (per_table && t % kAdamMaxTensors == 0) nch = 0;
+    if (numel[t] == 0) continue;
+    for (int k = 0; k < K; ++k)
+      if (streams[k] && !streams[k][t]) return fail(AAA_E_ARG, "%s: NULL pointer for tensor %d", who, t);
+    nch += adam_chunks(numel[t]);
+    if (nch > (1L << 30)) return fail(AAA_E_ARG, "%s: tensor %d too large", who, t);
+  }
+  return AAA_OK;
+}
+
+// Tensors [t0, t0 + kAdamMaxTensors) as one kernel table, the empty ones left out; returns its chunk count.
+template <int K>
+static int fill_table(TensorTable<K>& tab, int t0, int ntensors, const float* const* const (&streams)[K],
+                      const size_t* numel) {
+  memset(&tab, 0, sizeof tab);
+  int nch = 0;
+  for (int t = t0; t < std::min(ntensors, t0 + kAdamMaxTensors); ++t) {
+    if (numel[t] == 0) continue;
+    const int i = tab.n++;
+    tab.vec[i] = 1;
+    for (int k = 0; k < K; ++k) {
+      if (!streams[k]) continue;
+      tab.s[k][i] = const_cast<float*>(streams[k][t]);
+      if (!aligned16(streams[k][t])) tab.vec[i] = 0;
+    }
+    tab.numel[i] = numel[t];
+    tab.chunk0[i] = nch;
+    nch += (int)adam_chunks(numel[t]);
+  }
+  return nch;
+}
+
 extern "C" {
 
 int aaa_abi_version(void) { return AAA_ABI_VERSION; }
@@ -397,33 +439,18 @@ static int adam_impl(const aaa_adam_hparams* hp, long step, int* step_dev, const
   if (!(hp->lr >= 0.0) || !(hp->eps >= 0.0) || !(hp->beta1 >= 0.0 && hp->beta1 < 1.0) ||
       !(hp->beta2 >= 0.0 && hp->beta2 < 1.0) || !(hp->weight_decay >= 0.0))
     return fail(AAA_E_ARG, "%s: invalid hyper-parameters", who);
-  for (int t = 0; t < ntensors; ++t)   // every refusal before the device
-    if (numel[t] && (!params[t] || !grads[t] || !exp_avg[t] || !exp_avg_sq[t] || (hp->amsgrad && !max_exp_avg_sq[t])))
-      return fail(AAA_E_ARG, "%s: NULL pointer for tensor %d", who, t);
-  int r = check_device();
+  const float* const* const streams[5] = {params, grads, exp_avg, exp_avg_sq, hp->amsgrad ? max_exp_avg_sq : nullptr};
+  int r = check_tensors(who, ntensors, streams, numel, true);
   if (r) return r;
+  if ((r = check_device())) return r;
   AdamHost h{hp->lr, hp->beta1, hp->beta2, hp->eps, hp->weight_decay, step_dev ? 1 : step, hp->amsgrad ? 1 : 0,
              hp->maximize ? 1 : 0, guard, step_dev, stats};
   for (int t0 = 0; t0 < ntensors; t0 += kAdamMaxTensors) {
-    AdamTable tab;
-    memset(&tab, 0, sizeof tab);
-    int nch = 0;
-    for (int t = t0; t < std::min(ntensors, t0 + kAdamMaxTensors); ++t) {
-      if (numel[t] == 0) continue;
-      const int i = tab.n++;
-      tab.p[i] = params[t]; tab.g[i] = grads[t]; tab.m[i] = exp_avg[t]; tab.v[i] = exp_avg_sq[t];
-      tab.vmax[i] = h.amsgrad ? max_exp_avg_sq[t] : nullptr;
-      tab.numel[i] = numel[t];
-      tab.chunk0[i] = nch;
-      tab.vec[i] = aligned16(params[t]) && aligned16(grads[t]) && aligned16(exp_avg[t]) && aligned16(exp_avg_sq[t]) &&
-                   (!tab.vmax[i] || aligned16(tab.vmax[i]));
-      const long c = adam_chunks(numel[t]);
-      if (nch + c > (1L << 30)) return fail(AAA_E_ARG, "%s: tensor %d too large", who, t);
-      nch += (int)c;
-    }
+    TensorTable<5> tab;
+    const int nch = fill_table(tab, t0, ntensors, streams, numel);
     HIPCHK(adam_launch(tab, nch, h, stream, t0 + kAdamMaxTensors >= ntensors));
   }
-  if (ntensors == 0 && step_dev) HIPCHK(adam_launch(AdamTable{}, 0, h, stream, true));
+  if (ntensors == 0 && step_dev) HIPCHK(adam_launch(TensorTable<5>{}, 0, h, stream, true));
   return AAA_OK;
 }
 
@@ -445,35 +472,11 @@ int aaa_adam_step_counted(const aaa_adam_hparams* hp, int* step_dev, const float
 }
 
 // ---- gradient clipping by global norm ----
-// The argument checks of aaa_grad_norm / aaa_grad_scale, all before the device; *total: the chunk count.
-static int clip_check_grads(const char* who, int ntensors, const float* const* grads, const size_t* numel, long* total) {
-  if (ntensors < 0) return fail(AAA_E_ARG, "clip: %s: ntensors must be >= 0 (got %d)", who, ntensors);
-  if (ntensors > 0 && (!grads || !numel)) return fail(AAA_E_ARG, "clip: %s: NULL grads or numel array", who);
-  long nch = 0;
-  for (int t = 0; t < ntensors; ++t) {
-    if (numel[t] == 0) continue;
-    if (!grads[t]) return fail(AAA_E_ARG, "clip: %s: NULL pointer for tensor %d", who, t);
-    nch += adam_chunks(numel[t]);
-    if (nch > (1L << 30)) return fail(AAA_E_ARG, "clip: %s: tensor %d too large", who, t);
-  }
-  *total = nch;
-  return AAA_OK;
-}
-
-// Tensors [t0, t0 + kAdamMaxTensors) as one kernel table; returns its chunk count.
-static int clip_table(GradTable& tab, int t0, int ntensors, const float* const* grads, const size_t* numel) {
-  memset(&tab, 0, sizeof tab);
-  int nch = 0;
-  for (int t = t0; t < std::min(ntensors, t0 + kAdamMaxTensors); ++t) {
-    if (numel[t] == 0) continue;
-    const int i = tab.n++;
-    tab.g[i] = const_cast<float*>(grads[t]);
-    tab.numel[i] = numel[t];
-    tab.chunk0[i] = nch;
-    tab.vec[i] = aligned16(grads[t]);
-    nch += adam_chunks(numel[t]);
-  }
-  return nch;
+// The argument checks of aaa_grad_norm / aaa_grad_scale on the gradients, all before the device.
+static int clip_check_grads(const char* who, int ntensors, const float* const* const (&grads)[1], const size_t* numel) {
+  if (ntensors < 0) return fail(AAA_E_ARG, "%s: ntensors must be >= 0 (got %d)", who, ntensors);
+  if (ntensors > 0 && (!grads[0] || !numel)) return fail(AAA_E_ARG, "%s: NULL grads or numel array", who);
+  return check_tensors(who, ntensors, grads, numel, false);
 }
 
 size_t aaa_grad_norm_scratch_bytes(int ntensors, const size_t* numel) {
@@ -484,8 +487,8 @@ size_t aaa_grad_norm_scratch_bytes(int ntensors, const size_t* numel) {
 
 int aaa_grad_norm(double max_norm, int ntensors, const float* const* grads, const size_t* numel, float* stats,
                   void* scratch, hipStream_t stream) {
-  long total = 0;
-  int r = clip_check_grads("grad_norm", ntensors, grads, numel, &total);
+  const float* const* const streams[1] = {grads};
+  int r = clip_check_grads("clip: grad_norm", ntensors, streams, numel);
   if (r) return r;
   if (!stats || !scratch) return fail(AAA_E_ARG, "clip: grad_norm: NULL stats or scratch");
   if (!(max_norm > 0.0)) return fail(AAA_E_ARG, "clip: grad_norm: max_norm must be positive (+inf: norm only)");
@@ -495,8 +498,8 @@ int aaa_grad_norm(double max_norm, int ntensors, const float* const* grads, cons
   if (r) return r;
   int base = 0;   // the partial index runs on through the tables
   for (int t0 = 0; t0 < ntensors; t0 += kAdamMaxTensors) {
-    GradTable tab;
-    const int nch = clip_table(tab, t0, ntensors, grads, numel);
+    TensorTable<1> tab;
+    const int nch = fill_table(tab, t0, ntensors, streams, numel);
     HIPCHK(gradsq_launch(tab, nch, base, (double*)scratch, stream));
     base += nch;
   }
@@ -505,16 +508,16 @@ int aaa_grad_norm(double max_norm, int ntensors, const float* const* grads, cons
 }
 
 int aaa_grad_scale(const float* stats, int ntensors, float* const* grads, const size_t* numel, hipStream_t stream) {
-  long total = 0;
-  int r = clip_check_grads("grad_scale", ntensors, grads, numel, &total);
+  const float* const* const streams[1] = {grads};
+  int r = clip_check_grads("clip: grad_scale", ntensors, streams, numel);
   if (r) return r;
   if (!stats) return fail(AAA_E_ARG, "clip: grad_scale: NULL stats");
   if (!aligned16(stats)) return fail(AAA_E_ALIGN, "clip: grad_scale: stats must be 16-byte aligned");
   r = check_device();
   if (r) return r;
   for (int t0 = 0; t0 < ntensors; t0 += kAdamMaxTensors) {
-    GradTable tab;
-    const int nch = clip_table(tab, t0, ntensors, grads, numel);
+    TensorTable<1> tab;
+    const int nch = fill_table(tab, t0, ntensors, streams, numel);
     HIPCHK(grad_scale_launch(tab, nch, stats, stream));
   }
   return AAA_OK;
@@ -546,39 +549,20 @@ int aaa_rmsprop_step(const aaa_rmsprop_hparams* hp, long step, int* step_dev, co
   const bool mom = hp->momentum > 0.0, cent = hp->centered != 0;
   if (ntensors > 0 && (!params || !grads || !square_avg || !numel || (mom && !momentum_buf) || (cent && !grad_avg)))
     return fail(AAA_E_ARG, "rmsprop: NULL array (momentum > 0 needs momentum_buf, centered needs grad_avg)");
-  long nchunks = 0;   // of one table: the launch's grid
-  for (int t = 0; t < ntensors; ++t) {   // every refusal before the device
-    if (t % kAdamMaxTensors == 0) nchunks = 0;
-    if (numel[t] == 0) continue;
-    if (!params[t] || !grads[t] || !square_avg[t] || (mom && !momentum_buf[t]) || (cent && !grad_avg[t]))
-      return fail(AAA_E_ARG, "rmsprop: NULL pointer for tensor %d", t);
-    nchunks += adam_chunks(numel[t]);
-    if (nchunks > (1L << 30)) return fail(AAA_E_ARG, "rmsprop: tensor %d too large", t);
-  }
-  if (stats && !aligned16(stats)) return fail(AAA_E_ALIGN, "rmsprop: stats must be 16-byte aligned");
-  int r = check_device();
+  const float* const* const streams[5] = {params, grads, square_avg, mom ? momentum_buf : nullptr,
+                                          cent ? grad_avg : nullptr};
+  int r = check_tensors("rmsprop", ntensors, streams, numel, true);
   if (r) return r;
+  if (stats && !aligned16(stats)) return fail(AAA_E_ALIGN, "rmsprop: stats must be 16-byte aligned");
+  if ((r = check_device())) return r;
   RmspropHost h{hp->lr, hp->alpha, hp->eps, hp->weight_decay, hp->momentum, hp->lr_end, hp->anneal_steps,
                 step_dev ? 1 : step, cent ? 1 : 0, hp->maximize ? 1 : 0, hp->eps_in_sqrt ? 1 : 0, guard, step_dev, stats};
   for (int t0 = 0; t0 < ntensors; t0 += kAdamMaxTensors) {
-    RmspropTable tab;
-    memset(&tab, 0, sizeof tab);
-    int nch = 0;
-    for (int t = t0; t < std::min(ntensors, t0 + kAdamMaxTensors); ++t) {
-      if (numel[t] == 0) continue;
-      const int i = tab.n++;
-      tab.p[i] = params[t]; tab.g[i] = grads[t]; tab.v[i] = square_avg[t];
-      tab.b[i] = mom ? momentum_buf[t] : nullptr;
-      tab.a[i] = cent ? grad_avg[t] : nullptr;
-      tab.numel[i] = numel[t];
-      tab.chunk0[i] = nch;
-      tab.vec[i] = aligned16(params[t]) && aligned16(grads[t]) && aligned16(square_avg[t]) &&
-                   (!tab.b[i] || aligned16(tab.b[i])) && (!tab.a[i] || aligned16(tab.a[i]));
-      nch += adam_chunks(numel[t]);
-    }
+    TensorTable<5> tab;
+    const int nch = fill_table(tab, t0, ntensors, streams, numel);
     HIPCHK(rmsprop_launch(tab, nch, h, stream, t0 + kAdamMaxTensors >= ntensors));
   }
-  if (ntensors == 0 && step_dev) HIPCHK(rmsprop_launch(RmspropTable{}, 0, h, stream, true));
+  if (ntensors == 0 && step_dev) HIPCHK(rmsprop_launch(TensorTable<5>{}, 0, h, stream, true));
   return AAA_OK;
 }
 

@@ -59,37 +59,8 @@ class Adam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        for group in self.param_groups:
-            amsgrad = group["amsgrad"]
-            by_step = defaultdict(lambda: ([], [], [], [], []))
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                if p.grad.is_sparse:
-                    raise RuntimeError("Adam does not support sparse gradients")
-                if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
-                    raise RuntimeError("aaa_amd.optim.Adam: parameters must be contiguous fp32 tensors on the "
-                                       "gfx950 device (there is no CPU fallback)")
-                st = self.state[p]
-                if len(st) == 0:
-                    st["step"] = torch.tensor(0.0, dtype=torch.float32)
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    if amsgrad:
-                        st["max_exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                st["step"] += 1
-                lists = by_step[int(st["step"].item())]
-                lists[0].append(p)
-                lists[1].append(p.grad.contiguous())
-                lists[2].append(st["exp_avg"])
-                lists[3].append(st["exp_avg_sq"])
-                if amsgrad:
-                    lists[4].append(st["max_exp_avg_sq"])
-            hp = self._hp(group)
-            for step, (ps, gs, ms, vs, xs) in by_step.items():
-                N.adam_step(hp, step, ps, gs, ms, vs, xs if amsgrad else None,
-                            stream=N.stream_ptr(ps[0].device))
-                _bump_versions(ps)
+        _step_groups(self, "Adam", N.adam_step, lambda group: (
+            ("exp_avg", True), ("exp_avg_sq", True), ("max_exp_avg_sq", bool(group["amsgrad"]))))
         return loss
 
 
@@ -149,40 +120,45 @@ class RMSprop(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        for group in self.param_groups:
-            mom, cent = group["momentum"] > 0, bool(group["centered"])
-            by_step = defaultdict(lambda: ([], [], [], [], []))
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                if p.grad.is_sparse:
-                    raise RuntimeError("RMSprop does not support sparse gradients")
-                if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
-                    raise RuntimeError("aaa_amd.optim.RMSprop: parameters must be contiguous fp32 tensors on the "
-                                       "gfx950 device (there is no CPU fallback)")
-                st = self.state[p]
-                if len(st) == 0:
-                    st["step"] = torch.tensor(0.0, dtype=torch.float32)
-                    st["square_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    if mom:
-                        st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    if cent:
-                        st["grad_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                st["step"] += 1
-                lists = by_step[int(st["step"].item())]
-                lists[0].append(p)
-                lists[1].append(p.grad.contiguous())
-                lists[2].append(st["square_avg"])
-                if mom:
-                    lists[3].append(st["momentum_buffer"])
-                if cent:
-                    lists[4].append(st["grad_avg"])
-            hp = self._hp(group)
-            for step, (ps, gs, vs, bs, as_) in by_step.items():
-                N.rmsprop_step(hp, step, ps, gs, vs, bs if mom else None, as_ if cent else None,
-                               stream=N.stream_ptr(ps[0].device))
-                _bump_versions(ps)
+        _step_groups(self, "RMSprop", N.rmsprop_step, lambda group: (
+            ("square_avg", True), ("momentum_buffer", group["momentum"] > 0), ("grad_avg", bool(group["centered"]))))
         return loss
+
+
+def _step_groups(opt, name, launch, state_keys) -> None:
+    """The per-group loop of ``Adam.step`` / ``RMSprop.step``.  ``state_keys(group)``: the
+    (state key, wanted?) pairs of the group's buffers, in the order ``launch`` -- ``_native``'s
+    adam_step / rmsprop_step -- takes them after (hp, step, params, grads); a buffer not wanted
+    is never created and goes in as None.  One launch per distinct step value."""
+    for group in opt.param_groups:
+        keys = state_keys(group)
+        by_step = defaultdict(lambda: tuple([] for _ in range(2 + len(keys))))
+        for p in group["params"]:
+            if p.grad is None:
+                continue
+            if p.grad.is_sparse:
+                raise RuntimeError(f"{name} does not support sparse gradients")
+            if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
+                raise RuntimeError(f"aaa_amd.optim.{name}: parameters must be contiguous fp32 tensors on the "
+                                   "gfx950 device (there is no CPU fallback)")
+            st = opt.state[p]
+            if len(st) == 0:
+                st["step"] = torch.tensor(0.0, dtype=torch.float32)
+                for key, wanted in keys:
+                    if wanted:
+                        st[key] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            st["step"] += 1
+            lists = by_step[int(st["step"].item())]
+            lists[0].append(p)
+            lists[1].append(p.grad.contiguous())
+            for lst, (key, wanted) in zip(lists[2:], keys):
+                if wanted:
+                    lst.append(st[key])
+        hp = opt._hp(group)
+        for step, (ps, gs, *states) in by_step.items():
+            launch(hp, step, ps, gs, *[lst if wanted else None for lst, (_, wanted) in zip(states, keys)],
+                   stream=N.stream_ptr(ps[0].device))
+            _bump_versions(ps)
 
 
 def _rmsprop_hp(lr=1e-2, alpha=0.99, eps=1e-8, weight_decay=0.0, momentum=0.0, centered=False, maximize=False,
