@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define AAA_ABI_VERSION 11
+#define AAA_ABI_VERSION 12
 
 enum aaa_status {
   AAA_OK = 0,
@@ -296,10 +296,58 @@ int aaa_pair_flag_at(float* dst, int* base, hipStream_t stream);
  * With aaa_core_export's gates / c_t / h_t these are everything a checker
  * needs to evaluate the recurrence and its BPTT in fp64 on the kernels' own
  * inputs (tests/f32_split_ref.py, tests/test_gpu_f32_split.py).
+ * ABI 12, every cfg (these buffers are fp32 in both dtypes and every geometry):
+ * the operands, products and cotangents of the policy tail's GEMMs (everything
+ * after the ConvLSTM), read-only, F = T*B rows, frame f = t*B + b.  Each is a
+ * buffer of its own that no phase reuses, so with AAA_WS_ANSWER_HIDDEN and the
+ * two AAA_WS_QUERY_HIDDEN* a checker evaluates every tail layer in fp64 on the
+ * input the kernel really read (tests/tail_ref.py, tests/test_gpu_tail.py).
+ * Valid after the forward:
+ *   AAA_WS_TAIL_ANS       (F, ans_ld) fp32: the answer row, answer_processor.0's
+ *                         operand; ans_ld = 256 nq + 2 rounded up to 8, the
+ *                         padding columns zero;
+ *   AAA_WS_TAIL_GATES     (F, 1024) fp32: the policy core's gate activations,
+ *                         column 4u + g, g = (i, f, c~, o);
+ *   AAA_WS_TAIL_AO        (F, 256) fp32: answer_processor.2's output,
+ *   AAA_WS_TAIL_C, _H     (F, 256) fp32: the zero-state cell's c and h
+ *                         (configs without AAA_FLAG_STATEFUL_CORE);
+ *   AAA_WS_TAIL_AOX       (F, 512) fp32: the [answer | h_{t-1}] rows the stateful
+ *                         LSTMCell GEMM reads (after aaa_forward_resets: zeros in
+ *                         the h half of the rows with reset[t]),
+ *   AAA_WS_TAIL_CH, _CC   (T+1, B, 256) fp32: slot t = (h, c) entering step t,
+ *                         slot 0 the incoming core state,
+ *   AAA_WS_TAIL_QUERY     (F, 72 nq) fp32: the per-frame queries
+ *                         (AAA_FLAG_STATEFUL_CORE only).
+ * Valid after AAA_BWD_HEAD:
+ *   AAA_WS_TAIL_DY        (F, ldy) fp32: [dlogits | dvalues] concatenated,
+ *                         ldy = 2A rounded up to 4, the padding columns zero;
+ *   AAA_WS_TAIL_DGATES    (F, 1024) fp32: the gate pre-activations' cotangent;
+ *   AAA_WS_TAIL_DHID      (F, 512) fp32: answer_processor.0's pre-activation
+ *                         cotangent (through the ReLU mask);
+ *   AAA_WS_TAIL_DANS      (F, 184 nq | 256 nq stateful) fp32: the answer row's
+ *                         cotangent, the columns the readout backward reads;
+ *   AAA_WS_TAIL_DAO       (F, 256) fp32: answer_processor.2's output cotangent
+ *                         (configs without AAA_FLAG_STATEFUL_CORE);
+ *   AAA_WS_TAIL_DAOX      (F, 512) fp32: the [answer | h_{t-1}] rows' cotangent
+ *                         (the h half: the recurrent path only),
+ *   AAA_WS_TAIL_DQUERY, _DQ2, _DQ1  (F, 72 nq | 72 nq | 128) fp32: the cotangents
+ *                         of the queries and of the query MLP's two hidden
+ *                         pre-activations (AAA_FLAG_STATEFUL_CORE only).
+ * Not exposed: the stateful core's state carries dh, dc (one (B, 256) buffer
+ * each, rewritten by every step of the phase that produces them).  A checker
+ * reaches them through the next product: step t's carry dh is query.model.0's
+ * dgrad of step t+1's _DQ1 rows plus the h half of its _DAOX rows, and step t's
+ * _DGATES rows are checked from there.  The packed gradient accumulators are
+ * not exposed either: the HEAD phase unpacks every one of them into ``grads``.
  * AAA_E_ARG for an unknown region or one the cfg does not compute. */
 enum aaa_ws_region {
   AAA_WS_ANSWER_HIDDEN = 0, AAA_WS_QUERY_HIDDEN0 = 1, AAA_WS_QUERY_HIDDEN1 = 2,
-  AAA_WS_CORE_XH = 3, AAA_WS_CORE_DO = 4, AAA_WS_CORE_DX = 5
+  AAA_WS_CORE_XH = 3, AAA_WS_CORE_DO = 4, AAA_WS_CORE_DX = 5,
+  AAA_WS_TAIL_ANS = 6, AAA_WS_TAIL_GATES = 7, AAA_WS_TAIL_AO = 8, AAA_WS_TAIL_C = 9, AAA_WS_TAIL_H = 10,
+  AAA_WS_TAIL_AOX = 11, AAA_WS_TAIL_CH = 12, AAA_WS_TAIL_CC = 13, AAA_WS_TAIL_QUERY = 14,
+  AAA_WS_TAIL_DY = 15, AAA_WS_TAIL_DGATES = 16, AAA_WS_TAIL_DHID = 17, AAA_WS_TAIL_DANS = 18,
+  AAA_WS_TAIL_DAO = 19, AAA_WS_TAIL_DAOX = 20, AAA_WS_TAIL_DQUERY = 21, AAA_WS_TAIL_DQ2 = 22,
+  AAA_WS_TAIL_DQ1 = 23
 };
 int aaa_workspace_region(const aaa_cfg* cfg, int region, size_t* offset, size_t* bytes);
 
@@ -332,7 +380,13 @@ int aaa_timing_read(int kind, double* total_ms, long* launches);
  * 2*M*N*K of each GEMM; bytes for the HBM classes 3-4: the fp32 tensors each
  * frame must move; 0 for 5 and 11) and the kernel variant (tile / ring)
  * dispatched last.  A "launch" of classes 5-11 is one timed region (a group
- * of consecutive kernels of that class). */
+ * of consecutive kernels of that class).
+ * ABI 12: the variant of classes 7 and 8 ends with " | " and the kernel and
+ * arithmetic of every tail GEMM launched since the class was last read, in
+ * launch order, equal neighbours counted: "skinny8*18, CFK4/S6",
+ * "CFK4/S3 x2, CFK4/S3, CF/S3 x3" (skinny1 / skinny8: k_skinny_gemm<EP, 1 / 8>;
+ * CFK4, CF: the 32x64 4-way split-K and the 64x64 tile; f32 / S3 / S6: the
+ * fp32 MFMA, GemmCfgS3, GemmCfgS6; xN: N split-K slices summed by atomics). */
 typedef struct aaa_timer_stats {
   double total_ms;
   long launches;

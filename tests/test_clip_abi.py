@@ -47,7 +47,7 @@ def test_symbols_are_exported_and_bound():
         assert name in N.EXPORTS and hasattr(lib, name), name
         assert getattr(lib, name).argtypes is not None, name
     assert lib.aaa_grad_norm_scratch_bytes.restype is ctypes.c_size_t
-    assert lib.aaa_abi_version() == 11   # additive: no ABI bump
+    assert lib.aaa_abi_version() == 12   # additive: no ABI bump
     assert callable(N.grad_norm) and callable(N.grad_scale) and callable(N.grad_norm_scratch_bytes)
 
 

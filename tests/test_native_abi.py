@@ -33,7 +33,7 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_abi_version():
-    assert N.load().aaa_abi_version() == N.ABI_VERSION == 11
+    assert N.load().aaa_abi_version() == N.ABI_VERSION == 12
 
 
 def test_core_checker_regions():
@@ -44,7 +44,9 @@ def test_core_checker_regions():
     lib = N.load()
     src = open(HEADER).read()
     enum = dict((k, int(v)) for k, v in re.findall(r"AAA_WS_([A-Z0-9_]+)\s*=\s*(\d+)", src))
-    assert enum == {"ANSWER_HIDDEN": 0, "QUERY_HIDDEN0": 1, "QUERY_HIDDEN1": 2, "CORE_XH": 3, "CORE_DO": 4, "CORE_DX": 5}
+    core = {"ANSWER_HIDDEN": 0, "QUERY_HIDDEN0": 1, "QUERY_HIDDEN1": 2, "CORE_XH": 3, "CORE_DO": 4, "CORE_DX": 5}
+    assert {k: v for k, v in enum.items() if not k.startswith("TAIL_")} == core
+    assert sorted(enum.values()) == list(range(len(enum)))
     for name, val in enum.items():
         assert getattr(N, "WS_" + name) == val, name
     T, B, P = 20, 32, 121
@@ -65,7 +67,46 @@ def test_core_checker_regions():
         assert lib.aaa_workspace_region(ctypes.byref(bf), region, ctypes.byref(off), ctypes.byref(nb)) == -1
         assert b"region" in lib.aaa_last_error()
     assert lib.aaa_workspace_region(ctypes.byref(bf), N.WS_ANSWER_HIDDEN, ctypes.byref(off), ctypes.byref(nb)) == 0
-    assert lib.aaa_workspace_region(ctypes.byref(cfg), 6, ctypes.byref(off), ctypes.byref(nb)) == -1
+    for unknown in (-1, len(enum)):
+        assert lib.aaa_workspace_region(ctypes.byref(cfg), unknown, ctypes.byref(off), ctypes.byref(nb)) == -1
+
+
+def test_tail_checker_regions():
+    """ABI 12: the policy tail's operands, products and cotangents as workspace regions -- granted for fp32 and
+    bf16 configs alike (fp32 buffers in both), their sizes from the cfg, inside the workspace, no two overlapping
+    (nor the older regions), and AAA_E_ARG for the regions of the other core kind."""
+    lib = N.load()
+    T, B = 3, 9
+    every = ("ANS", "GATES", "DY", "DGATES", "DHID", "DANS")
+    zero = ("AO", "C", "H", "DAO")
+    state = ("AOX", "CH", "CC", "QUERY", "DAOX", "DQUERY", "DQ2", "DQ1")
+    assert sorted(every + zero + state) == sorted(k[8:] for k in dir(N) if k.startswith("WS_TAIL_"))
+    for nq, A in ((4, 18), (8, 5)):
+        F, qd, ans_ld, ldy = T * B, 72 * nq, (256 * nq + 2 + 7) // 8 * 8, (2 * A + 3) // 4 * 4
+        for dt in (N.F32, N.BF16):
+            for sc in (0, 1):
+                cfg = N.Cfg(B, T, 84, 84, nq, A, dt, N.FLAG_STATEFUL_CORE if sc else 0)
+                ws = lib.aaa_workspace_bytes(ctypes.byref(cfg))
+                cols = {"ANS": ans_ld, "GATES": 1024, "DY": ldy, "DGATES": 1024, "DHID": 512,
+                        "DANS": (256 if sc else 184) * nq, "AO": 256, "C": 256, "H": 256, "DAO": 256, "AOX": 512,
+                        "DAOX": 512, "QUERY": qd, "DQUERY": qd, "DQ2": qd, "DQ1": 128}
+                spans = []
+                off, nb = ctypes.c_size_t(), ctypes.c_size_t()
+                for name in every + (state if sc else zero) + ("ANSWER_HIDDEN",) + (("QUERY_HIDDEN0", "QUERY_HIDDEN1") if sc else ()):
+                    rc = lib.aaa_workspace_region(ctypes.byref(cfg), getattr(N, "WS_" + ("" if "HIDDEN" in name else "TAIL_") + name),
+                                                  ctypes.byref(off), ctypes.byref(nb))
+                    assert rc == 0, (name, nq, dt, sc)
+                    if "HIDDEN" not in name:
+                        want = (T + 1) * B * 256 * 4 if name in ("CH", "CC") else F * cols[name] * 4
+                        assert nb.value == want, (name, nb.value, want)
+                    assert off.value % 16 == 0 and off.value + nb.value <= ws, name
+                    spans.append((off.value, off.value + nb.value, name))
+                spans.sort()
+                assert all(a[1] <= b[0] for a, b in zip(spans, spans[1:])), spans
+                for name in (zero if sc else state):
+                    assert lib.aaa_workspace_region(ctypes.byref(cfg), getattr(N, "WS_TAIL_" + name), ctypes.byref(off),
+                                                    ctypes.byref(nb)) == -1, name
+                    assert b"region" in lib.aaa_last_error()
 
 
 @pytest.mark.parametrize("H,W,hw", [(84, 84, (11, 11)), (168, 168, (21, 21)), (210, 160, (27, 20))])

@@ -42,7 +42,7 @@ def test_symbols_are_exported_and_bound():
     for name in ("aaa_forward_resets", "aaa_backward_resets"):
         assert name in N.EXPORTS
         assert hasattr(N.load(), name)
-    assert N.load().aaa_abi_version() == 11   # additive: no bump
+    assert N.load().aaa_abi_version() == 12   # additive: no bump
 
 
 @pytest.mark.parametrize("call,phases", [(_fwd, N.FWD_ALL), (_bwd, N.BWD_ALL)], ids=["forward", "backward"])

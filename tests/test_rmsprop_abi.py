@@ -54,7 +54,7 @@ def test_symbol_is_exported_and_bound():
     lib = N.load()
     assert "aaa_rmsprop_step" in N.EXPORTS and hasattr(lib, "aaa_rmsprop_step")
     assert lib.aaa_rmsprop_step.argtypes is not None and len(lib.aaa_rmsprop_step.argtypes) == 13
-    assert lib.aaa_abi_version() == N.ABI_VERSION == 11   # additive: no ABI bump
+    assert lib.aaa_abi_version() == N.ABI_VERSION == 12   # additive: no ABI bump
     assert callable(N.rmsprop_step)
     # the struct as include/aaa.h lays it out: 6 doubles, a long, 3 ints (+ tail padding)
     assert [f[0] for f in N.RmspropHP._fields_] == ["lr", "alpha", "eps", "weight_decay", "momentum", "lr_end",

@@ -72,7 +72,7 @@ def test_symbols_are_exported_and_bound():
     for name in ("aaa_unroll_begin", "aaa_unroll_record"):
         assert name in N.EXPORTS and hasattr(lib, name)
         assert len(getattr(lib, name).argtypes) == 3
-    assert lib.aaa_abi_version() == N.ABI_VERSION == 11   # additive: no ABI bump
+    assert lib.aaa_abi_version() == N.ABI_VERSION == 12   # additive: no ABI bump
     assert callable(N.unroll_begin) and callable(N.unroll_record)
 
 

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AAA_LIB") or os.path.join(_HERE, "libaaa.so")
 
 F32, BF16 = 0, 1
-ABI_VERSION = 11  # include/aaa.h AAA_ABI_VERSION
+ABI_VERSION = 12  # include/aaa.h AAA_ABI_VERSION
 E_STRANDED = -5   # AAA_E_STRANDED
 BWD_HEAD, BWD_CORE, BWD_VISION, BWD_ALL = 1, 2, 4, 7
 FWD_VISION, FWD_CORE, FWD_TAIL, FWD_ALL = 1, 2, 4, 7
@@ -64,6 +64,10 @@ FLAG_DEFER_STRANDED = 4
 # include/aaa.h enum aaa_ws_region
 WS_ANSWER_HIDDEN, WS_QUERY_HIDDEN0, WS_QUERY_HIDDEN1 = 0, 1, 2
 WS_CORE_XH, WS_CORE_DO, WS_CORE_DX = 3, 4, 5   # fp32 configs only (ABI 11)
+# the policy tail's operands, products and cotangents, every cfg (ABI 12)
+(WS_TAIL_ANS, WS_TAIL_GATES, WS_TAIL_AO, WS_TAIL_C, WS_TAIL_H, WS_TAIL_AOX, WS_TAIL_CH, WS_TAIL_CC, WS_TAIL_QUERY,
+ WS_TAIL_DY, WS_TAIL_DGATES, WS_TAIL_DHID, WS_TAIL_DANS, WS_TAIL_DAO, WS_TAIL_DAOX, WS_TAIL_DQUERY, WS_TAIL_DQ2,
+ WS_TAIL_DQ1) = range(6, 24)
 
 
 class TimerStats(ctypes.Structure):

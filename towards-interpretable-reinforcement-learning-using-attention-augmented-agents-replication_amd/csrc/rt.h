@@ -147,6 +147,8 @@ struct Timers {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pending[AAA_TIMER_N];
   double work[AAA_TIMER_N] = {};
   std::string variant[AAA_TIMER_N];
+  // the tail GEMMs' dispatch since the class was last read (tail_ran): (kernel/arithmetic, equal launches in a row)
+  std::vector<std::pair<std::string, int>> ran[AAA_TIMER_N];
   std::vector<hipEvent_t> pool;
   hipEvent_t get() {
     if (!pool.empty()) { hipEvent_t e = pool.back(); pool.pop_back(); return e; }
@@ -310,18 +312,30 @@ static hipError_t step_gemm(const T* W, int ldw, int wrows, const G* src, const 
 // (gemm.h GemmCfgS3), ~1e-5 relative per product.
 // g_tail6 (set per call of the fp32 path when f32_split6()): the three-way
 // split at fp32 accuracy (gemm.h GemmCfgS6).
+// g_tail_kind (set with them): the timer class (AAA_TIMER_TAIL_FWD / _BWD) whose variant records which
+// kernel and arithmetic each tail GEMM of the call took (tail_ran); -1 outside a forward / backward call.
 extern thread_local bool g_tail3, g_tail6;
+extern thread_local int g_tail_kind;
 struct TailPrecision {
   bool prev3, prev6;
-  explicit TailPrecision(bool split3, bool split6 = false) : prev3(g_tail3), prev6(g_tail6) {
+  int prevk;
+  explicit TailPrecision(bool split3, bool split6 = false, int kind = -1)
+      : prev3(g_tail3), prev6(g_tail6), prevk(g_tail_kind) {
     g_tail3 = split3;
     g_tail6 = split6;
+    g_tail_kind = kind;
   }
   ~TailPrecision() {
     g_tail3 = prev3;
     g_tail6 = prev6;
+    g_tail_kind = prevk;
   }
 };
+// One tail GEMM launch for the timers (while enabled): ``kernel`` = skinny1 / skinny8 / CFK4 / CF, on the
+// arithmetic of g_tail3 / g_tail6 (the skinny kernels: plain fp32 FMAs, none named), in ``slices`` K slices.
+// aaa_timing_stats appends the launches to the class's variant in order, equal neighbours counted:
+// "skinny8*15, CFK4/S6, CF/S3 x3" (x3: three split-K slices accumulating with atomics).
+void tail_ran(const char* kernel, bool mfma, int slices = 1);
 template <class C> struct S3Of { using type = GemmCfgS3<C::BI, C::BJ, C::BK, C::WI, C::WJ, C::WK>; };
 template <class C> struct S6Of { using type = GemmCfgS6<C::BI, C::BJ, C::BK, C::WI, C::WJ, C::WK>; };
 
@@ -384,7 +398,10 @@ static hipError_t head_gemm(const Rows& pa, const Rows& pb, const EP& ep, int Mi
     if (g_tail3) return run(typename S3Of<decltype(cfg0)>::type{});
     return run(cfg0);
   };
-  if (mode == 0 && tiles < 192) return splitk(CFK4{});
+  if (mode == 0 && tiles < 192) {
+    tail_ran("CFK4", true, splitk_slices(K, CFK4::BK, std::max(nsplit, 1)));
+    return splitk(CFK4{});
+  }
   // bf16 path, 64x64 tiles: the operands split once at their LDS commit (hi, lo part tiles, gemm_kernel_s6l),
   // not per wave per fragment read -- the same products in the same order (AAA_TAIL_S3L=1, ablation builds: A/B)
   if (mode == 0 && g_tail3 && ab_int("AAA_TAIL_S3L", 0) && DeepLd<LA_>::fits(pa.src, pa.ld, pa.nrows) &&
@@ -396,7 +413,10 @@ static hipError_t head_gemm(const Rows& pa, const Rows& pb, const EP& ep, int Mi
     return launch_gemm<C, A, B>(typename A::Params{pa.src, pa.ld, pa.nrows}, typename B::Params{pb.src, pb.ld, pb.nrows},
                                 ep, Mi, Nj, K, nsplit, st);
   }
-  if (mode == 1 || (mode == 0 && tiles >= 192)) return splitk(CF{});
+  if (mode == 1 || (mode == 0 && tiles >= 192)) {
+    tail_ran("CF", true, splitk_slices(K, CF::BK, std::max(nsplit, 1)));
+    return splitk(CF{});
+  }
 #ifdef AAA_ABLATION   // the measured-slower tail tiles (AAA_HEAD_TILE 2-5)
   if (mode == 3) return splitk(CFK{});
   if (mode == 4) return splitk(CFK4{});
@@ -462,6 +482,7 @@ template <class EP>
 static hipError_t tail_gemm(const Rows& pa, const Rows& pb, const EP& ep, int Mi, int Nj, int K, hipStream_t st) {
   if (Nj <= kSkinnyMaxCols && K % 4 == 0 && pa.ld % 4 == 0 && pb.ld % 4 == 0 && ab_int("AAA_SKINNY", 1)) {
     const int blocks = cdiv(cdiv(Mi, 4), 4);
+    tail_ran(Nj == 1 ? "skinny1" : "skinny8", false);
     if (Nj == 1)
       hipLaunchKernelGGL((k_skinny_gemm<EP, 1>), dim3(blocks), dim3(256), 0, st, pa.src, pa.ld, Mi, pb.src, pb.ld, Nj,
                          K, ep);

@@ -1183,7 +1183,7 @@ template <typename T>
 int backward_impl(const Layout& L, const aaa_io* io, int phases, hipStream_t st, const float* reset) {
   // bf16 path: the fp32 tail GEMMs on the bf16 MFMA with split operands (AAA_TAIL_SPLIT3=0: fp32 MFMA)
   TailPrecision tail_prec(std::is_same<T, __bf16>::value && env_int("AAA_TAIL_SPLIT3", 1),
-                          std::is_same<T, float>::value && f32_split6());
+                          std::is_same<T, float>::value && f32_split6(), AAA_TIMER_TAIL_BWD);
   const BwdCtx c{L, io, (char*)io->workspace, (const char*)io->packed, io->params, io->grads, st, reset};
   const bool vision = (phases & AAA_BWD_VISION) != 0;
   LstmGrads core_unpack{};   // the ConvLSTM grads' reference tensors, unpacked with the vision grads when both run here

@@ -7,6 +7,7 @@ namespace aaa {
 
 thread_local std::string g_err;
 thread_local bool g_tail3 = false, g_tail6 = false;
+thread_local int g_tail_kind = -1;
 
 int fail(int code, const char* fmt, ...) {
   char buf[512];
@@ -371,6 +372,19 @@ hipError_t stream_order(hipStream_t from, hipStream_t to) {
 }
 
 Timers g_timers;
+
+void tail_ran(const char* kernel, bool mfma, int slices) {
+  const int kind = g_tail_kind;
+  if (kind < 0 || kind >= AAA_TIMER_N) return;
+  std::lock_guard<std::mutex> lk(g_timers.mu);
+  if (!g_timers.on) return;
+  std::string tok = kernel;
+  if (mfma) tok += g_tail6 ? "/S6" : g_tail3 ? "/S3" : "/f32";
+  if (slices > 1) tok += strf(" x%d", slices);
+  auto& v = g_timers.ran[kind];
+  if (!v.empty() && v.back().first == tok) ++v.back().second;
+  else v.emplace_back(std::move(tok), 1);
+}
 
 std::string strf(const char* fmt, ...) {
   char buf[256];

@@ -190,7 +190,7 @@ template <typename T>
 int forward_impl(const Layout& L, const aaa_io* io, hipStream_t st, int phases, const float* reset) {
   // bf16 path: the fp32 tail GEMMs on the bf16 MFMA with split operands (AAA_TAIL_SPLIT3=0: fp32 MFMA)
   TailPrecision tail_prec(std::is_same<T, __bf16>::value && env_int("AAA_TAIL_SPLIT3", 1),
-                          std::is_same<T, float>::value && f32_split6());
+                          std::is_same<T, float>::value && f32_split6(), AAA_TIMER_TAIL_FWD);
   char* ws = (char*)io->workspace;
   const char* pk = (const char*)io->packed;
   const float* prm = io->params;

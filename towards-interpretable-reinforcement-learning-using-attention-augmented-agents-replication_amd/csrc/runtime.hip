@@ -121,6 +121,7 @@ int aaa_timing_enable(int on) {
   g_timers.on = on != 0;
   for (double& w : g_timers.work) w = 0.0;
   for (auto& v : g_timers.variant) v.clear();
+  for (auto& v : g_timers.ran) v.clear();
   for (auto& v : g_timers.pending) {
     for (auto& pr : v) { g_timers.pool.push_back(pr.first); g_timers.pool.push_back(pr.second); }
     v.clear();
@@ -145,7 +146,15 @@ int aaa_timing_stats(int kind, aaa_timer_stats* out) {
     std::lock_guard<std::mutex> lk(g_timers.mu);
     v.swap(g_timers.pending[kind]);
     out->work = g_timers.work[kind];
-    snprintf(out->variant, sizeof out->variant, "%s", g_timers.variant[kind].c_str());
+    std::string var = g_timers.variant[kind];
+    // the tail classes: which kernel and arithmetic each GEMM launch since the last read took (rt.h tail_ran)
+    const char* sep = " | ";
+    for (const auto& r : g_timers.ran[kind]) {
+      var += sep + r.first + (r.second > 1 ? strf("*%d", r.second) : std::string());
+      sep = ", ";
+    }
+    g_timers.ran[kind].clear();
+    snprintf(out->variant, sizeof out->variant, "%s", var.c_str());
     g_timers.work[kind] = 0.0;
   }
   double tot = 0.0;
@@ -172,6 +181,41 @@ int aaa_workspace_region(const aaa_cfg* cfg, int region, size_t* offset, size_t*
   const size_t F = L.F;
   switch (region) {
     case AAA_WS_ANSWER_HIDDEN: *offset = L.hid1; *bytes = F * 512 * 4; return AAA_OK;
+    // the policy tail's GEMM operands, products and cotangents: fp32 in both dtypes and every geometry, each in
+    // a buffer of its own that no phase reuses (build_layout), so a checker's fp64 reference of one tail layer
+    // reads that layer's input as the kernel stored it
+    case AAA_WS_TAIL_ANS: *offset = L.ans; *bytes = F * L.ans_ld * 4; return AAA_OK;
+    case AAA_WS_TAIL_GATES: *offset = L.LG; *bytes = F * 1024 * 4; return AAA_OK;
+    case AAA_WS_TAIL_DY: *offset = L.dY; *bytes = F * L.ldy * 4; return AAA_OK;
+    case AAA_WS_TAIL_DGATES: *offset = L.dLG; *bytes = F * 1024 * 4; return AAA_OK;
+    case AAA_WS_TAIL_DHID: *offset = L.dH1; *bytes = F * 512 * 4; return AAA_OK;
+    case AAA_WS_TAIL_DANS: *offset = L.dAns; *bytes = F * L.da * 4; return AAA_OK;
+    case AAA_WS_TAIL_AO:
+    case AAA_WS_TAIL_C:
+    case AAA_WS_TAIL_H:
+    case AAA_WS_TAIL_DAO:
+      if (L.sc) break;
+      *offset = region == AAA_WS_TAIL_AO ? L.AO : region == AAA_WS_TAIL_C ? L.LC : region == AAA_WS_TAIL_H ? L.LH : L.dAO;
+      *bytes = F * 256 * 4;
+      return AAA_OK;
+    case AAA_WS_TAIL_AOX:
+    case AAA_WS_TAIL_DAOX:
+      if (!L.sc) break;
+      *offset = region == AAA_WS_TAIL_AOX ? L.AOX : L.dAOX; *bytes = F * 512 * 4; return AAA_OK;
+    case AAA_WS_TAIL_CH:
+    case AAA_WS_TAIL_CC:
+      if (!L.sc) break;
+      *offset = region == AAA_WS_TAIL_CH ? L.CH : L.CC; *bytes = (size_t)(L.T + 1) * L.B * 256 * 4; return AAA_OK;
+    case AAA_WS_TAIL_QUERY:
+    case AAA_WS_TAIL_DQUERY:
+    case AAA_WS_TAIL_DQ2:
+      if (!L.sc) break;
+      *offset = region == AAA_WS_TAIL_QUERY ? L.Qf : region == AAA_WS_TAIL_DQUERY ? L.dQf : L.dq2s;
+      *bytes = F * (size_t)L.qd * 4;
+      return AAA_OK;
+    case AAA_WS_TAIL_DQ1:
+      if (!L.sc) break;
+      *offset = L.dq1s; *bytes = F * 128 * 4; return AAA_OK;
     case AAA_WS_QUERY_HIDDEN0:
       if (!L.sc) break;
       *offset = L.q1s; *bytes = F * 128 * 4; return AAA_OK;

@@ -50,7 +50,10 @@ class UnrollRunner:
     def workspace_region(self, workspace, region: int, shape=None):
         """A product inside ``workspace`` (aaa_workspace_region): an fp32 view,
         (T*B, n) by default, e.g. N.WS_ANSWER_HIDDEN = relu(answer_processor.0),
-        or of ``shape`` (one -1 allowed), e.g. N.WS_CORE_XH as (T+1, B*h*w, 192)."""
+        or of ``shape`` (one -1 allowed), e.g. N.WS_CORE_XH as (T+1, B*h*w, 192).
+        The policy tail's operands, products and cotangents (N.WS_TAIL_*, every
+        dtype; include/aaa.h lists their shapes and when each is valid) come the
+        same way, e.g. N.WS_TAIL_CH as (T+1, B, 256)."""
         off, nb = ctypes.c_size_t(), ctypes.c_size_t()
         N.check(self.lib.aaa_workspace_region(ctypes.byref(self.cfg), int(region), ctypes.byref(off),
                                               ctypes.byref(nb)), "workspace_region")
