@@ -219,6 +219,13 @@ static int chunk_steps(const Layout& L) {
   return std::max(1, std::min({c, L.T, L.fchunk / L.B}));
 }
 bool f32_split6();   // fp32 path: large GEMMs as bf16x6 split products (rt_core.hip)
+// A frame-resident forward (k_vision_fwd / k_vision_fwd_f32) can run on this layout.  The learner's
+// forward then stores no Xp, so the backward never trusts the Xp region's contents where this holds:
+// its layered launches rebuild the image from the observation (conv1_wgrad_frames).  Stated on the
+// layout alone, not on AAA_VIS_FRAMES / AAA_VIS_BWD_FRAMES, which may change between the two calls.
+inline bool vis_frames_layout(const Layout& L) {
+  return vis_fits(L.H, L.W, L.H1, L.W1, L.h, L.w) && (L.dt == AAA_BF16 || f32_split6());
+}
 // An id of another family, or one this family holds for the other operand type only, runs tile 4
 // (every family has a 4).  < 0: the variable names an id that no family holds; the caller
 // refuses (tile_unknown).
@@ -595,7 +602,8 @@ bool f32_split6();
 template <typename T> int pack_impl(const Layout& L, const float* prm, char* pk, hipStream_t st);
 template <typename T, typename OT>
 int vision_fwd(const Layout& L, int F, const char* pk, const float* prm, const void* frames, T* Xp, T* Y1, OT* out,
-               int out_ld, hipStream_t st, bool xp_full = true, std::string* ran = nullptr);   // ran <- the kernels taken
+               int out_ld, hipStream_t st, bool xp_full = true, std::string* ran = nullptr,   // ran <- the kernels taken
+               bool resident_xp = true);   // false: a frame-resident kernel stores no Xp (the learner; ran says "no Xp")
 // reset: the episode-start mask (T, B) of aaa_forward_resets / aaa_backward_resets (fp32 only), or null
 template <typename T>
 int forward_impl(const Layout& L, const aaa_io* io, hipStream_t st, int phases, const float* reset = nullptr);

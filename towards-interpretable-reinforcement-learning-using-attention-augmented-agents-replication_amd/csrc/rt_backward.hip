@@ -394,10 +394,12 @@ int lstm_wgrad(const T* dz, const T* xh, int rows, int h, int w, float* gW, hipS
 }
 
 // conv1 weight gradient over n frames whose bordered RGBx image (Xp) is
-// rebuilt from the observation in chunks of L.xpc frames into the chunk
-// buffer xpbuf: the forward keeps no Xp, and each chunk is written and read
-// back while it sits in the memory-side cache (256 MB) instead of all F
-// frames' images round-tripping through HBM between the two passes.
+// rebuilt from the observation in chunks of L.xpc frames into xpbuf (the
+// chunk buffer, or the frames' slice of a whole-batch region: L.xpc = F):
+// the forward keeps no Xp (a chunk buffer, or a frame-resident encoder, which
+// stores none in the learner), and a chunk is written and read back while it
+// sits in the memory-side cache (256 MB) instead of all F frames' images
+// round-tripping through HBM between the two passes.
 template <typename T>
 static int conv1_wgrad_frames(const Layout& L, const T* dy1, const void* frames, int n, T* xpbuf, float* gW,
                               hipStream_t s) {
@@ -416,7 +418,7 @@ static int conv1_wgrad_frames(const Layout& L, const T* dy1, const void* frames,
 // Vision encoder backward over F frames in descriptor-sized chunks: conv2
 // weight grad (gW2 +=), conv2 dgrad -> dY1 with conv1's bias grad (gb1 +=),
 // conv1 weight grad (gW1 +=); accumulators zeroed by the caller.  frames:
-// xp is the L.xpc-frame chunk buffer rebuilt from them (conv1_wgrad_frames);
+// xp is rebuilt from them L.xpc frames at a time (conv1_wgrad_frames);
 // null: xp holds all F frames' images (the component entries).
 template <typename T>
 int vision_bwd(const Layout& L, const char* pk, const T* dy2, const T* y1, T* xp, T* dy1, int F,
@@ -745,10 +747,12 @@ static int chunk_vision(const BwdCtx& c, int lo, int hi, hipStream_t vs) {
                  vision_bwd_variant(on, std::is_same<T, float>::value, false));
   const void* fr = (const char*)c.io->frames + f0 * L.H * L.W * 3 * (L.fu8 ? 1 : 4);
   const bool chunked = L.xpc < L.F;   // Xp chunk buffer: rebuilt from the observation
+  // and so is these frames' own slice of a whole-batch Xp region wherever the forward may have stored none
+  const bool rebuild = chunked || vis_frames_layout(L);
   return vision_bwd_alone<T>(L, c.pk, fr, c.Wt<T>(L.dY2) + f0 * L.P * 64, c.Wt<T>(L.Y1) + f0 * L.P1 * 32,
                              chunked ? c.Wt<T>(L.Xp) : c.Wt<T>(L.Xp) + f0 * (L.H + 2) * (L.W + 2) * 4,
                              c.Wt<T>(L.dY1) + f0 * L.P1 * 32, nullptr, 0, F1, c.Wf(L.gWp2), c.Wf(L.gWp1),
-                             c.grads + L.poff[C0B], vs, chunked ? fr : nullptr, nullptr);
+                             c.grads + L.poff[C0B], vs, rebuild ? fr : nullptr, nullptr);
 }
 
 // dx_t (conv2's output gradient dY2) of steps [lo, hi) in one launch on ``s``:
@@ -1169,9 +1173,11 @@ static int vision_backward(const BwdCtx& c, int phases, const LstmGrads& core_un
   TimerScope tim(AAA_TIMER_VISION_BWD, c.st, vision_here ? 0.0 : (double)L.F * vision_bwd_flop(L),
                  vision_bwd_variant(vbwd_on<T>(L, L.F), std::is_same<T, float>::value));
   if (!vision_here) {   // VISION alone: frame-resident, or its chunk work over all frames, here
+    // (layered: the image rebuilt from the observation where Xp is a chunk buffer or the forward may have stored none)
+    const bool rebuild = L.xpc < L.F || vis_frames_layout(L);
     const int rc = vision_bwd_alone<T>(L, c.pk, c.io->frames, c.Wt<T>(L.dY2), c.Wt<T>(L.Y1), c.Wt<T>(L.Xp),
                                        c.Wt<T>(L.dY1), nullptr, 0, L.F, c.Wf(L.gWp2), c.Wf(L.gWp1),
-                                       c.grads + L.poff[C0B], c.st, L.xpc < L.F ? c.io->frames : nullptr, nullptr);
+                                       c.grads + L.poff[C0B], c.st, rebuild ? c.io->frames : nullptr, nullptr);
     if (rc) return rc;
   }
   HIPCHK(unpack_cv(vision_here ? c.Wf(L.gWpl) : nullptr, c.Wf(L.gbl), core_unpack, c.Wf(L.gWp2),

@@ -148,26 +148,32 @@ static int vision_fwd_chunk(const Layout& L, int F, const char* pk, const float*
 
 template <typename T, typename OT>
 int vision_fwd(const Layout& L, int F, const char* pk, const float* prm, const void* frames, T* Xp, T* Y1,
-                      OT* out, int out_ld, hipStream_t st, bool xp_full, std::string* ran) {
+                      OT* out, int out_ld, hipStream_t st, bool xp_full, std::string* ran, bool resident_xp) {
+  // The frame-resident kernels read the observation themselves: Xp is only a by-product for a layered
+  // backward, stored for the component and checker entries (resident_xp) and never for the learner, whose
+  // backward rebuilds the image wherever one of them can run (rt.h vis_frames_layout).
+  T* const rxp = xp_full && resident_xp ? Xp : nullptr;
   if constexpr (std::is_same<T, __bf16>::value && std::is_same<OT, __bf16>::value) {
     // bf16: the frame-resident encoder (vision.h), one launch; AAA_VIS_FRAMES=0 -> the layered kernels
     if (vis_fits(L.H, L.W, L.H1, L.W1, L.h, L.w) && env_int("AAA_VIS_FRAMES", 1)) {
       VisFwdParams vp{frames, (const __bf16*)(pk + L.k_Wp1), prm + L.poff[C0B], (const __bf16*)(pk + L.k_Wp2),
-                      prm + L.poff[C1B], xp_full ? Xp : nullptr, Y1, out, out_ld, F, L.H, L.W, L.H1, L.W1, L.h, L.w};
+                      prm + L.poff[C1B], rxp, Y1, out, out_ld, F, L.H, L.W, L.H1, L.W1, L.h, L.w};
       HIPCHK(L.fu8 ? vision_fwd_frames<uint8_t>(vp, device_cus(), st) : vision_fwd_frames<float>(vp, device_cus(), st));
-      if (ran) *ran = "frame-resident conv1 + conv2 [kernel: k_vision_fwd]";
+      if (ran) *ran = std::string("frame-resident conv1 + conv2 [kernel: k_vision_fwd]") + (rxp ? "" : ", no Xp");
       return AAA_OK;
     }
   }
   if constexpr (std::is_same<T, float>::value && std::is_same<OT, float>::value) {
     // fp32 split products: the frame-resident encoder (vision_f32.h), one launch, which also writes the
-    // fp32 Xp and Y1 the layered backward reads; AAA_VIS_FRAMES=0 -> the layered kernels
+    // fp32 Y1 the backward reads; AAA_VIS_FRAMES=0 -> the layered kernels
     if (f32_split6() && vis_fits(L.H, L.W, L.H1, L.W1, L.h, L.w) && env_int("AAA_VIS_FRAMES", 1)) {
       VisF32Params vp{frames, (const bf16x8*)(pk + L.k_W1s), prm + L.poff[C0B], (const bf16x8*)(pk + L.k_W2s),
-                      prm + L.poff[C1B], xp_full ? Xp : nullptr, Y1, out, out_ld, F, L.H, L.W, L.H1, L.W1, L.h, L.w};
+                      prm + L.poff[C1B], rxp, Y1, out, out_ld, F, L.H, L.W, L.H1, L.W1, L.h, L.w};
       HIPCHK(L.fu8 ? vision_fwd_frames_f32<uint8_t>(vp, device_cus(), st)
                    : vision_fwd_frames_f32<float>(vp, device_cus(), st));
-      if (ran) *ran = "frame-resident conv1 + conv2 (bf16x6 split products) [kernel: k_vision_fwd_f32]";
+      if (ran)
+        *ran = std::string("frame-resident conv1 + conv2 (bf16x6 split products) [kernel: k_vision_fwd_f32]") +
+               (rxp ? "" : ", no Xp");
       return AAA_OK;
     }
   }
@@ -215,7 +221,8 @@ int forward_impl(const Layout& L, const aaa_io* io, hipStream_t st, int phases, 
   {  // conv1 + conv2 over all T*B frames -> XH[:, :, 0:64] of every slot
     TimerScope tim(AAA_TIMER_VISION_FWD, st, (double)F * vision_fwd_flop(L), "conv1 + conv2 (vision encoder)");
     std::string ran;   // the kernels the dispatch took, for the timer's variant
-    const int rc = vision_fwd<T, T>(L, F, pk, prm, io->frames, Wt(L.Xp), Wt(L.Y1), Wt(L.XH), 192, st, L.xpc >= F, &ran);
+    const int rc = vision_fwd<T, T>(L, F, pk, prm, io->frames, Wt(L.Xp), Wt(L.Y1), Wt(L.XH), 192, st, L.xpc >= F, &ran,
+                                    false);
     if (rc) return rc;
     tim.variant += ": " + ran;
   }
@@ -521,11 +528,11 @@ static int forward_tail(const Layout& L, const aaa_io* io, hipStream_t st, const
 template int pack_impl<float>(const Layout&, const float*, char*, hipStream_t);
 template int pack_impl<__bf16>(const Layout&, const float*, char*, hipStream_t);
 template int vision_fwd<float, float>(const Layout&, int, const char*, const float*, const void*, float*, float*,
-                                      float*, int, hipStream_t, bool, std::string*);
+                                      float*, int, hipStream_t, bool, std::string*, bool);
 template int vision_fwd<__bf16, __bf16>(const Layout&, int, const char*, const float*, const void*, __bf16*, __bf16*,
-                                        __bf16*, int, hipStream_t, bool, std::string*);
+                                        __bf16*, int, hipStream_t, bool, std::string*, bool);
 template int vision_fwd<__bf16, float>(const Layout&, int, const char*, const float*, const void*, __bf16*, __bf16*,
-                                       float*, int, hipStream_t, bool, std::string*);
+                                       float*, int, hipStream_t, bool, std::string*, bool);
 template int forward_impl<float>(const Layout&, const aaa_io*, hipStream_t, int, const float*);
 template int forward_impl<__bf16>(const Layout&, const aaa_io*, hipStream_t, int, const float*);
 

@@ -3,8 +3,9 @@
 // end to end -- the observation (uint8 or fp32 (H, W, 3)) into a zero-bordered
 // RGBx bf16 image in LDS, conv1 (8x8 / 4, pad 1) from that image into a
 // zero-bordered Y1 image in LDS, conv2 (4x4 / 2, pad 2) from it into the
-// ConvLSTM operand slot -- and writes the bordered frame image (Xp) and Y1 to
-// HBM only as the weight-gradient operands.  It replaces the three launches of
+// ConvLSTM operand slot -- and writes Y1 and, where the caller asks for it (the
+// XP instantiation: the checker entries; the learner stores none), the bordered
+// frame image (Xp) to HBM only as the weight-gradient operands.  It replaces the three launches of
 // the layered path (frames_rgbx, conv1, conv2: C3 107 + 221 + 125 us), whose
 // im2col tiles re-read every frame pixel from L2 four (conv1) to sixteen times.
 //
@@ -46,7 +47,8 @@ inline bool vis_fits(int H, int W, int H1, int W1, int h, int w) {
          H * W <= kVisNG * 256 * 4 && H1 * W1 <= 16 * 32 && h * w <= 128;
 }
 
-template <typename TI>
+// XP: the bordered frame image Xp is stored (p.Xp set); off, the instantiation holds no store loop.
+template <typename TI, bool XP>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) k_vision_fwd(VisFwdParams p) {
   __shared__ __attribute__((aligned(16))) unsigned char xim[kVisXB];
   __shared__ __attribute__((aligned(16))) unsigned char yim[kVisYB];
@@ -126,7 +128,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     if (f + (int)gridDim.x < p.F) fetch(f + gridDim.x);   // next frame's pixels, under this one's convs
     barrier_lds();   // RGBx image complete (and the previous frame's conv2 done with the Y1 image); the
                      // next frame's loads stay in flight (no vmcnt drain, unlike __syncthreads)
-    if (p.Xp) {        // the bordered frame for conv1's weight gradient
+    if constexpr (XP) {   // the bordered frame for conv1's weight gradient
       u32x4* xo = reinterpret_cast<u32x4*>(p.Xp + (size_t)f * (p.H + 2) * Wp * 4);
       const int n = (p.H + 2) * Wp / 2;
       for (int i0 = 0; i0 < n; i0 += 1024) {   // 4 pieces in flight per thread
@@ -235,7 +237,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
 template <typename TI>
 inline hipError_t vision_fwd_frames(const VisFwdParams& p, int cus, hipStream_t st) {
   if (!vis_fits(p.H, p.W, p.H1, p.W1, p.h, p.w) || p.F < 1) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((k_vision_fwd<TI>), dim3(std::min(p.F, cus)), dim3(256), 0, st, p);
+  if (p.Xp) hipLaunchKernelGGL((k_vision_fwd<TI, true>), dim3(std::min(p.F, cus)), dim3(256), 0, st, p);
+  else hipLaunchKernelGGL((k_vision_fwd<TI, false>), dim3(std::min(p.F, cus)), dim3(256), 0, st, p);
   return hipGetLastError();
 }
 

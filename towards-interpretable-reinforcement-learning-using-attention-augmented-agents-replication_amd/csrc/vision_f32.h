@@ -7,9 +7,10 @@
 // Per frame:
 //   image  the observation (H, W, 3) -> zero-bordered RGBx bf16 image in LDS
 //          (uint8 frames: exact, one image; fp32 frames: the hi / mid / lo bf16
-//          parts of the frame, one image after the other) and, from the same
-//          registers, the fp32 bordered image Xp in HBM (conv1's weight-gradient
-//          operand: bit for bit k_frames_rgbx's).
+//          parts of the frame, one image after the other) and, where the caller
+//          asks for it (the XP instantiation: the checker entries; the learner
+//          stores none), from the same registers the fp32 bordered image Xp in HBM
+//          (the layered conv1 weight gradient's operand: bit for bit k_frames_rgbx's).
 //   conv1  D[32][P1] from the image against the PRE-SPLIT conv1 weights (hi / mid /
 //          lo bf16 fragments, streamed from L2 a few k steps ahead), all of a
 //          wave's column blocks (<= 4) accumulated in registers.  Products per k
@@ -17,7 +18,7 @@
 //          frames add, before them, the image passes x_lo: W_hi and x_mid: W_mid,
 //          W_hi -- all exact zeros on integer-valued frames, so the result is
 //          then bit for bit the uint8 instantiation's.
-//   Y1     + bias -> fp32 to HBM (the layered backward reads it) and, split once,
+//   Y1     + bias -> fp32 to HBM (the backward reads it) and, split once,
 //          into the hi / mid / lo planes of a zero-bordered Y1 image in LDS.
 //   conv2  D[64][P] from the three planes against the pre-split conv2 weights
 //          (streamed from L2), six products per k step in SPLIT6's order, + bias
@@ -97,7 +98,9 @@ __device__ __forceinline__ void vf_conv1_pass(const unsigned char* xim, const bf
   }
 }
 
-template <typename TI>
+// XP: the fp32 bordered image Xp is stored (p.Xp set).  Off, the instantiation holds none of the store's
+// conversions, border stores or address arithmetic.
+template <typename TI, bool XP>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) k_vision_fwd_f32(VisF32Params p) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[kVfLds];
   __shared__ float sb[96];
@@ -149,7 +152,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     if (part == 1) return mid;
     return (__bf16)(r - (float)mid);
   };
-  // the fetched pixels' part ``part`` into the RGBx image; with xo, the pixels themselves into Xp's interior
+  // the fetched pixels' part ``part`` into the RGBx image; with xo (XP only), the pixels themselves into Xp's interior
   auto build = [&](int part, float* xo) {
 #pragma unroll
     for (int i = 0; i < kVisNG; ++i) {
@@ -161,7 +164,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         for (int j = 0; j < 4; ++j)
           *reinterpret_cast<bf16x4*>(d + j * 8) = bf16x4{part_of(chan(i, 3 * j), part), part_of(chan(i, 3 * j + 1), part),
                                                          part_of(chan(i, 3 * j + 2), part), (__bf16)0.f};
-        if (xo) {
+        if (XP && xo) {
           f32x4* xd = reinterpret_cast<f32x4*>(xo + ((size_t)(y + 1) * Wp + x + 1) * 4);
 #pragma unroll
           for (int j = 0; j < 4; ++j) xd[j] = f32x4{chan(i, 3 * j), chan(i, 3 * j + 1), chan(i, 3 * j + 2), 0.f};
@@ -195,13 +198,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
   for (; f < p.F; f += gridDim.x) {
     int wl = lane;   // laundered: the weight fragments are streamed per frame, not hoisted out of the frame loop
     asm volatile("" : "+v"(wl));
-    float* const xo = p.Xp ? p.Xp + (size_t)f * (p.H + 2) * Wp * 4 : nullptr;
+    float* xo = nullptr;
+    if constexpr (XP) xo = p.Xp + (size_t)f * (p.H + 2) * Wp * 4;
     // the image's border (plane lo of the previous frame lay over part of it), and Xp's
     for (int i = tid; i < 2 * Wp + 2 * p.H; i += 256) {
       const int px = i < 2 * Wp ? (i < Wp ? i : (p.H + 1) * Wp + i - Wp)
                                 : (1 + ((i - 2 * Wp) >> 1)) * Wp + ((i & 1) ? Wp - 1 : 0);
       *reinterpret_cast<uint2*>(xim + px * 8) = uint2{0u, 0u};
-      if (xo) *reinterpret_cast<f32x4*>(xo + (size_t)px * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+      if constexpr (XP) *reinterpret_cast<f32x4*>(xo + (size_t)px * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     f32x16 acc[4];
 #pragma unroll
@@ -348,7 +352,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
 template <typename TI>
 inline hipError_t vision_fwd_frames_f32(const VisF32Params& p, int cus, hipStream_t st) {
   if (!vis_fits(p.H, p.W, p.H1, p.W1, p.h, p.w) || p.F < 1) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((k_vision_fwd_f32<TI>), dim3(std::min(p.F, cus)), dim3(256), 0, st, p);
+  if (p.Xp) hipLaunchKernelGGL((k_vision_fwd_f32<TI, true>), dim3(std::min(p.F, cus)), dim3(256), 0, st, p);
+  else hipLaunchKernelGGL((k_vision_fwd_f32<TI, false>), dim3(std::min(p.F, cus)), dim3(256), 0, st, p);
   return hipGetLastError();
 }
 
