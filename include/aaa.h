@@ -339,6 +339,38 @@ int aaa_pair_flag_at(float* dst, int* base, hipStream_t stream);
  * dgrad of step t+1's _DQ1 rows plus the h half of its _DAOX rows, and step t's
  * _DGATES rows are checked from there.  The packed gradient accumulators are
  * not exposed either: the HEAD phase unpacks every one of them into ``grads``.
+ * Added after ABI 12 without a bump (additive: probe aaa_core_layout by name),
+ * bf16 configs only (fp32 configs: AAA_E_ARG; they have AAA_WS_CORE_* and
+ * aaa_core_export): the bf16 ConvLSTM recurrence's buffers exactly as the
+ * kernels store them, read-only, each a buffer of its own that no later phase
+ * reuses, M = B*h*w pixel rows per step, P = h*w per frame, frame b of step t
+ * at rows t*M + b*P ..:
+ *   AAA_BF16_WS_XH     (T+1, M, 192) bf16, row-major: slot t = [x_t | h_{t-1}],
+ *                      slot 0's h half the incoming h0 rounded to bf16, slot
+ *                      t+1's h half h_t (the only stored copy); after the forward;
+ *   AAA_BF16_WS_C      (T+1, M, 128) fp32: slot s+1 = c_s, slot 0 = c0; after
+ *                      the forward;
+ *   AAA_BF16_WS_GATES  (T, M, 512) post-activation gates in the gate storage
+ *                      type (aaa_core_layout: fp16, or fp32); after the forward;
+ *   AAA_BF16_WS_DO     (T, M, 128) fp32: the readout's cotangent of h_t; after
+ *                      AAA_BWD_HEAD;
+ *   AAA_BF16_WS_DZ     (T, M, 512) bf16, row-major, column 4*ch + gate: the gate
+ *                      pre-activations' cotangent dZ_t, the dgrad's and the
+ *                      weight gradient's operand; after AAA_BWD_CORE;
+ *   AAA_BF16_WS_DX     (T, M, 64) bf16, row-major: the cotangent of conv2's
+ *                      output x_t; after AAA_BWD_CORE.
+ * aaa_core_layout reports the gate storage size in bytes (2 or 4) and which of
+ * _C / _GATES / _DO keep their slices channel-quad-major: bit 0 (1) _C, bit 1
+ * (2) _GATES, bit 2 (4) _DO; 0 = all row-major (pixel-major, channel fastest;
+ * gates column 4*ch + gate, gate = i, f, c~, o), which is exactly where
+ * aaa_core_elem_bytes reports non-zero sizes.  A channel-quad-major buffer
+ * keeps every (step, frame) slice of P pixels at its row-major position and
+ * size and permutes only the inside of that slice -- per frame, not per step:
+ * element (pixel pp of the frame, channel ch[, gate]) of the slice sits at
+ *   ((ch >> 2) * P + pp) * 4 + (ch & 3)                  _C, _DO (fp32 elements)
+ *   ((ch >> 2) * P + pp) * 16 + (ch & 3) * 4 + gate      _GATES (gate elements)
+ * (tests/convlstm_bf16_ref.py de-permutes with these on the host;
+ * tests/test_gpu_convlstm_bf16.py).
  * AAA_E_ARG for an unknown region or one the cfg does not compute. */
 enum aaa_ws_region {
   AAA_WS_ANSWER_HIDDEN = 0, AAA_WS_QUERY_HIDDEN0 = 1, AAA_WS_QUERY_HIDDEN1 = 2,
@@ -347,9 +379,12 @@ enum aaa_ws_region {
   AAA_WS_TAIL_AOX = 11, AAA_WS_TAIL_CH = 12, AAA_WS_TAIL_CC = 13, AAA_WS_TAIL_QUERY = 14,
   AAA_WS_TAIL_DY = 15, AAA_WS_TAIL_DGATES = 16, AAA_WS_TAIL_DHID = 17, AAA_WS_TAIL_DANS = 18,
   AAA_WS_TAIL_DAO = 19, AAA_WS_TAIL_DAOX = 20, AAA_WS_TAIL_DQUERY = 21, AAA_WS_TAIL_DQ2 = 22,
-  AAA_WS_TAIL_DQ1 = 23
+  AAA_WS_TAIL_DQ1 = 23,
+  AAA_BF16_WS_XH = 24, AAA_BF16_WS_C = 25, AAA_BF16_WS_GATES = 26, AAA_BF16_WS_DO = 27, AAA_BF16_WS_DZ = 28,
+  AAA_BF16_WS_DX = 29
 };
 int aaa_workspace_region(const aaa_cfg* cfg, int region, size_t* offset, size_t* bytes);
+int aaa_core_layout(const aaa_cfg* cfg, int* gate_bytes, int* cqm_mask);
 
 /* ---- optional kernel timing (benchmarks) ----
  * While enabled, the runtime records a hipEvent pair on the launch stream

@@ -4,7 +4,9 @@ that times out instead of returning results computed from a stale half.
 
 Reference: the recurrence they run is attention.py:117-125 (ConvLSTMCell
 forward) and its autograd backward (main_mp.py:77).  These tests only pin the
-health channel -- the numerics of the same launches are covered by
+health channel -- the numerics of the paired kernels are held to fp64 step by
+step, on their own stored operands, by test_gpu_convlstm_bf16.py (selection
+"pairs"), and end to end at this shape by
 test_gpu_parity.py::test_c3_c4_full_size_bf16_vs_emulated_oracle[128].
 """
 import numpy as np

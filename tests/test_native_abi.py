@@ -109,6 +109,70 @@ def test_tail_checker_regions():
                     assert b"region" in lib.aaa_last_error()
 
 
+def test_bf16_core_checker_regions(monkeypatch):
+    """After ABI 12, additive: the bf16 recurrence's buffers as workspace regions (AAA_BF16_WS_*) and
+    aaa_core_layout -- granted for bf16 configs in every geometry (row-major per-step, channel-quad-major
+    frame-resident and band mode), refused for fp32 ones; their sizes from the cfg and the gate storage type;
+    inside the workspace, 16-byte aligned, no two overlapping (nor the tail's and the mask regions); and
+    aaa_core_layout's mask is 0 exactly where aaa_core_elem_bytes reports non-zero sizes."""
+    lib = N.load()
+    src = open(HEADER).read()
+    enum = dict((k, int(v)) for k, v in re.findall(r"AAA_BF16_WS_([A-Z0-9_]+)\s*=\s*(\d+)", src))
+    assert enum == {"XH": 24, "C": 25, "GATES": 26, "DO": 27, "DZ": 28, "DX": 29}
+    for name, val in enum.items():
+        assert getattr(N, "BF16_WS_" + name) == val, name
+    assert (N.CQM_C, N.CQM_G, N.CQM_DO) == (1, 2, 4)
+    off, nb = ctypes.c_size_t(), ctypes.c_size_t()
+    ge, he, gl, mask = (ctypes.c_int() for _ in range(4))
+    masks = set()
+    # (env, B, T, H, W): per-step default, forced frame-resident / paired, the production batch, band mode and
+    # the per-step launches on its grid, a grid neither kernel family takes
+    geos = (({}, 2, 3, 84, 84), ({"AAA_FRAMES_FWD": "1", "AAA_FRAMES_BWD": "1"}, 2, 3, 84, 84),
+            ({"AAA_FRAMES_FWD": "2", "AAA_FRAMES_BWD": "2"}, 9, 2, 84, 84),
+            ({"AAA_FRAMES_FWD": "1", "AAA_FRAMES_BWD": "0"}, 3, 4, 64, 64), ({}, 256, 20, 84, 84),
+            ({}, 5, 3, 168, 168), ({"AAA_FRAMES_BAND": "0"}, 5, 3, 168, 168), ({}, 1, 1, 210, 160))
+    for env, B, T, H, W in geos:
+        for k in ("AAA_FRAMES_FWD", "AAA_FRAMES_BWD", "AAA_FRAMES_BAND"):
+            monkeypatch.delenv(k, raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        h, w = N.grid(H, W)
+        M = B * h * w
+        cfg = N.Cfg(B, T, H, W, 4, 18, N.BF16, 0)
+        ws = lib.aaa_workspace_bytes(ctypes.byref(cfg))
+        assert lib.aaa_core_layout(ctypes.byref(cfg), ctypes.byref(gl), ctypes.byref(mask)) == 0
+        assert lib.aaa_core_elem_bytes(ctypes.byref(cfg), ctypes.byref(ge), ctypes.byref(he)) == 0
+        assert gl.value in (2, 4) and 0 <= mask.value <= 7
+        assert (mask.value == 0) == (ge.value != 0) == (he.value != 0), (env, B, H, mask.value, ge.value)
+        if ge.value:
+            assert ge.value == gl.value and he.value == 2
+        masks.add(mask.value)
+        want = {"XH": (T + 1) * M * 192 * 2, "C": (T + 1) * M * 128 * 4, "GATES": T * M * 512 * gl.value,
+                "DO": T * M * 128 * 4, "DZ": T * M * 512 * 2, "DX": T * M * 64 * 2}
+        spans = []
+        for name in list(want) + ["WS_ANSWER_HIDDEN", "WS_TAIL_ANS", "WS_TAIL_GATES", "WS_TAIL_DY", "WS_TAIL_DANS"]:
+            region = getattr(N, name if name.startswith("WS_") else "BF16_WS_" + name)
+            assert lib.aaa_workspace_region(ctypes.byref(cfg), region, ctypes.byref(off), ctypes.byref(nb)) == 0, name
+            if name in want:
+                assert nb.value == want[name], (name, nb.value, want[name])
+            assert off.value % 16 == 0 and off.value + nb.value <= ws, name
+            spans.append((off.value, off.value + nb.value, name))
+        spans.sort()
+        assert all(a[1] <= b[0] for a, b in zip(spans, spans[1:])), spans
+        f32 = N.Cfg(B, T, H, W, 4, 18, N.F32, 0)
+        for name in want:
+            assert lib.aaa_workspace_region(ctypes.byref(f32), getattr(N, "BF16_WS_" + name), ctypes.byref(off),
+                                            ctypes.byref(nb)) == -1, name
+            assert b"region" in lib.aaa_last_error()
+        assert lib.aaa_core_layout(ctypes.byref(f32), ctypes.byref(gl), ctypes.byref(mask)) == 0
+        assert (gl.value, mask.value) == (4, 0)
+        assert lib.aaa_workspace_region(ctypes.byref(cfg), 30, ctypes.byref(off), ctypes.byref(nb)) == -1
+    assert masks == {0, 7}, masks   # both layouts were seen
+    assert lib.aaa_core_layout(ctypes.byref(cfg), None, ctypes.byref(mask)) == -1
+    bad = N.Cfg(2, 3, 84, 84, 5, 18, N.BF16, 0)
+    assert lib.aaa_core_layout(ctypes.byref(bad), ctypes.byref(gl), ctypes.byref(mask)) == -1
+
+
 @pytest.mark.parametrize("H,W,hw", [(84, 84, (11, 11)), (168, 168, (21, 21)), (210, 160, (27, 20))])
 def test_grid(H, W, hw):
     assert N.grid(H, W) == hw

@@ -42,6 +42,7 @@ EXPORTS = (
     "aaa_vision_enc_f32_workspace_bytes", "aaa_vision_enc_f32_bwd",
     "aaa_rmsprop_step",
     "aaa_unroll_begin", "aaa_unroll_record",
+    "aaa_core_layout",
 )
 # include/aaa.h enum aaa_timer
 TIMER_FWD_STEP, TIMER_BPTT_STEP, TIMER_CORE_WGRAD, TIMER_ATTN_FWD, TIMER_ATTN_BWD = 0, 1, 2, 3, 4
@@ -68,6 +69,9 @@ WS_CORE_XH, WS_CORE_DO, WS_CORE_DX = 3, 4, 5   # fp32 configs only (ABI 11)
 (WS_TAIL_ANS, WS_TAIL_GATES, WS_TAIL_AO, WS_TAIL_C, WS_TAIL_H, WS_TAIL_AOX, WS_TAIL_CH, WS_TAIL_CC, WS_TAIL_QUERY,
  WS_TAIL_DY, WS_TAIL_DGATES, WS_TAIL_DHID, WS_TAIL_DANS, WS_TAIL_DAO, WS_TAIL_DAOX, WS_TAIL_DQUERY, WS_TAIL_DQ2,
  WS_TAIL_DQ1) = range(6, 24)
+# the bf16 recurrence's buffers as stored, bf16 configs only (include/aaa.h AAA_BF16_WS_*; aaa_core_layout)
+BF16_WS_XH, BF16_WS_C, BF16_WS_GATES, BF16_WS_DO, BF16_WS_DZ, BF16_WS_DX = range(24, 30)
+CQM_C, CQM_G, CQM_DO = 1, 2, 4   # aaa_core_layout's mask: which of _C / _GATES / _DO are channel-quad-major
 
 
 class TimerStats(ctypes.Structure):
@@ -220,6 +224,7 @@ def load(path: str = LIB_PATH):
             "aaa_adam_step_clipped": (I, [ctypes.POINTER(AdamHP), P, P, P, I, P, P, P, P, P, P, P]),
             "aaa_rmsprop_step": (I, [ctypes.POINTER(RmspropHP), ctypes.c_long, P, P, P, I, P, P, P, P, P, P, P]),
             "aaa_core_elem_bytes": (I, [ctypes.POINTER(Cfg), ctypes.POINTER(I), ctypes.POINTER(I)]),
+            "aaa_core_layout": (I, [ctypes.POINTER(Cfg), ctypes.POINTER(I), ctypes.POINTER(I)]),
             "aaa_workspace_region": (I, [ctypes.POINTER(Cfg), I, ctypes.POINTER(ctypes.c_size_t),
                                          ctypes.POINTER(ctypes.c_size_t)]),
             "aaa_reinforce": (I, [I, I, I, P, P, P, ctypes.c_double, P, P, P, P]),

@@ -174,6 +174,8 @@ int aaa_timing_stats(int kind, aaa_timer_stats* out) {
   return rc;
 }
 
+static int core_gate_bytes(const Layout& L);   // bytes of one stored gate activation (below)
+
 int aaa_workspace_region(const aaa_cfg* cfg, int region, size_t* offset, size_t* bytes) {
   if (!offset || !bytes) return fail(AAA_E_ARG, "workspace_region: NULL output");
   Layout L;
@@ -234,9 +236,36 @@ int aaa_workspace_region(const aaa_cfg* cfg, int region, size_t* offset, size_t*
       else { *offset = L.dY2; *bytes = F * L.P * 64 * 4; }
       return AAA_OK;
     }
+    // the bf16 recurrence's buffers as build_layout lays them out (bf16 only, every geometry: the slices of
+    // _C / _GATES / _DO are channel-quad-major where aaa_core_layout's mask says so), each a buffer of its own
+    case AAA_BF16_WS_XH:
+    case AAA_BF16_WS_C:
+    case AAA_BF16_WS_GATES:
+    case AAA_BF16_WS_DO:
+    case AAA_BF16_WS_DZ:
+    case AAA_BF16_WS_DX: {
+      if (L.dt != AAA_BF16) break;
+      const size_t M = (size_t)L.B * L.P;
+      if (region == AAA_BF16_WS_XH) { *offset = L.XH; *bytes = (size_t)(L.T + 1) * M * 192 * 2; }
+      else if (region == AAA_BF16_WS_C) { *offset = L.Cst; *bytes = (size_t)(L.T + 1) * M * 128 * 4; }
+      else if (region == AAA_BF16_WS_GATES) { *offset = L.Gt; *bytes = F * L.P * 512 * core_gate_bytes(L); }
+      else if (region == AAA_BF16_WS_DO) { *offset = L.dO; *bytes = F * L.P * 128 * 4; }
+      else if (region == AAA_BF16_WS_DZ) { *offset = L.dZ; *bytes = F * L.P * 512 * 2; }
+      else { *offset = L.dY2; *bytes = F * L.P * 64 * 2; }
+      return AAA_OK;
+    }
     default: break;
   }
   return fail(AAA_E_ARG, "workspace_region: region %d not computed by this cfg", region);
+}
+
+int aaa_core_layout(const aaa_cfg* cfg, int* gate_bytes, int* cqm_mask) {
+  if (!gate_bytes || !cqm_mask) return fail(AAA_E_ARG, "core_layout: NULL output");
+  Layout L;
+  if (int r = build_layout(cfg, L)) return r;
+  *gate_bytes = core_gate_bytes(L);
+  *cqm_mask = cqm_layout(L);
+  return AAA_OK;
 }
 
 int aaa_grid(int H, int W, int* h, int* w) {

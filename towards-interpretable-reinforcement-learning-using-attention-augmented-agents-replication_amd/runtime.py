@@ -47,19 +47,31 @@ class UnrollRunner:
     def state_shape(self):
         return (self.B, self.h, self.w, 128)
 
-    def workspace_region(self, workspace, region: int, shape=None):
-        """A product inside ``workspace`` (aaa_workspace_region): an fp32 view,
-        (T*B, n) by default, e.g. N.WS_ANSWER_HIDDEN = relu(answer_processor.0),
-        or of ``shape`` (one -1 allowed), e.g. N.WS_CORE_XH as (T+1, B*h*w, 192).
-        The policy tail's operands, products and cotangents (N.WS_TAIL_*, every
-        dtype; include/aaa.h lists their shapes and when each is valid) come the
-        same way, e.g. N.WS_TAIL_CH as (T+1, B, 256)."""
+    def workspace_region(self, workspace, region: int, shape=None, dtype=torch.float32):
+        """A product inside ``workspace`` (aaa_workspace_region): a view of
+        ``dtype`` (fp32 unless given), (T*B, n) by default, e.g.
+        N.WS_ANSWER_HIDDEN = relu(answer_processor.0), or of ``shape`` (one -1
+        allowed), e.g. N.WS_CORE_XH as (T+1, B*h*w, 192).  The policy tail's
+        operands, products and cotangents (N.WS_TAIL_*, every dtype;
+        include/aaa.h lists their shapes and when each is valid) come the same
+        way, e.g. N.WS_TAIL_CH as (T+1, B, 256); the bf16 recurrence's buffers
+        (N.BF16_WS_*) in their storage types, e.g. N.BF16_WS_XH as (T+1, B*h*w,
+        192) with dtype=torch.bfloat16 (core_layout() gives the gate type and
+        which slices are channel-quad-major)."""
         off, nb = ctypes.c_size_t(), ctypes.c_size_t()
         N.check(self.lib.aaa_workspace_region(ctypes.byref(self.cfg), int(region), ctypes.byref(off),
                                               ctypes.byref(nb)), "workspace_region")
         F = self.T * self.B
-        flat = workspace[off.value:off.value + nb.value].view(torch.float32)
-        return flat.view(F, nb.value // (4 * F)) if shape is None else flat.view(*shape)
+        flat = workspace[off.value:off.value + nb.value].view(dtype)
+        return flat.view(F, flat.numel() // F) if shape is None else flat.view(*shape)
+
+    def core_layout(self):
+        """(gate dtype, mask) of the recurrence's stored products (aaa_core_layout): torch.float16 or
+        torch.float32 gate activations, and which of the N.BF16_WS_C / _GATES / _DO slices are
+        channel-quad-major (N.CQM_C | N.CQM_G | N.CQM_DO; 0: all row-major)."""
+        ge, mask = ctypes.c_int(), ctypes.c_int()
+        N.check(self.lib.aaa_core_layout(ctypes.byref(self.cfg), ctypes.byref(ge), ctypes.byref(mask)), "core_layout")
+        return (torch.float16 if ge.value == 2 else torch.float32), mask.value
 
     def relu_masks(self, workspace):
         """The on/off pattern of every ReLU the hand-written backward masks with,
