@@ -56,7 +56,7 @@ constexpr int kSC1 = 16;            // buffer load / store cache policy: sc1 (cr
 // keep their row-major positions and sizes; only their inside is permuted.
 __host__ __device__ __forceinline__ int cqm4(int pp, int ch, int P) { return ((ch >> 2) * P + pp) * 4 + (ch & 3); }
 __host__ __device__ __forceinline__ int cqmg(int pp, int ch, int P) { return ((ch >> 2) * P + pp) * 16 + (ch & 3) * 4; }
-// Which slices are channel-quad-major (cqm_layout's mask; the others row-major):
+// Which slices are channel-quad-major (RecurPlan::cqm's mask, rt.h; the others row-major):
 constexpr int kCqmC = 1, kCqmG = 2, kCqmDO = 4;
 // offset of channel ch of pixel pp in a 128-channel fp32 slice / in a gate slice (4 gates per channel)
 __host__ __device__ __forceinline__ int slc4(int pp, int ch, int P, bool q) { return q ? cqm4(pp, ch, P) : pp * 128 + ch; }

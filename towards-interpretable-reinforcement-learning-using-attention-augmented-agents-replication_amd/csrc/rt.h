@@ -102,13 +102,8 @@ int check_device();
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // ------------------------------------------------- paired-kernel reports --
-// The paired frame-resident kernels (two cooperating workgroups per frame)
-// bound their partner waits (common.h pair_wait).  A timed-out wait adds 1 to
-// this device's report word: pinned host memory mapped into the device, so the
-// host reads it without a copy or a sync.  Every aaa_forward / aaa_backward
-// entry consumes pending reports and fails with AAA_E_STRANDED (the results of
-// the call that stranded are invalid); aaa_pair_status syncs a stream first.
-// Allocated once per process on first use, never freed (no HIP call at exit).
+// Timed-out partner waits of the multi-workgroup frame kernels (common.h pair_wait), counted per device in a
+// host-mapped report word (rt_core.hip); every aaa_forward / aaa_backward entry consumes them: AAA_E_STRANDED.
 int pair_budget(int T);    // partner-wait budget of a T-step launch, 100-MHz ticks
 int* pair_report(int dev);  // this device's report word, device-mapped (nullptr: cannot map)
 int* pair_flag_base(int dev);  // aaa_pair_flag's own snapshot of it, device-mapped
@@ -123,12 +118,7 @@ inline int report_word(const char* what, int** rep) {
   return AAA_OK;
 }
 
-// ------------------------------------------------------------ aux stream --
-// Work that is off the sequential ConvLSTM chain (the batched x-part of the
-// forward, every weight/bias gradient and dx/conv backward) is issued on a
-// per-device low-priority stream, chunked every few steps and ordered against
-// the caller's stream by events; the caller's stream waits for it before the
-// call returns (fork/join inside each call).  Created lazily, once per device.
+// ----------------------------------------- aux and side streams (rt_core.hip) --
 hipStream_t aux_stream();   // nullptr unless AAA_OVERLAP=1 (measured slower on C2, round 1)
 hipStream_t side_stream();  // the backward HEAD phase's weight gradients (rt_core.hip); nullptr: AAA_SIDE=0
 // Record a pooled event on ``s`` (everything enqueued on s so far).
@@ -196,9 +186,6 @@ inline double attn_bwd_bytes(int P, int nq, int oesz = 4) {
   return oesz * 128.0 * P + 4.0 * (128.0 * P + nq * P + 184.0 * nq + 72.0 * nq);
 }
 
-// Step-kernel tile choice (env AAA_STEP_TILE / AAA_BPTT_TILE override; the ids:
-// step_tiles.h).  The default picks by how many 32x32 output tiles the step has,
-// i.e. how many waves it can feed; measured on C2.
 // (env_int: common.h)
 // A/B-only knobs (the same-box comparisons of tools/gpu_ab*.sh): read from the
 // environment only in -DAAA_ABLATION builds (make ablation -> libaaa_ablation.so,
@@ -218,7 +205,7 @@ static int chunk_steps(const Layout& L) {
   const int c = ab_int("AAA_CHUNK", ab_int("AAA_OVERLAP", 0) ? 4 : L.T);
   return std::max(1, std::min({c, L.T, L.fchunk / L.B}));
 }
-bool f32_split6();   // fp32 path: large GEMMs as bf16x6 split products (rt_core.hip)
+bool f32_split6();   // fp32 path: large GEMMs as bf16x6 split products on the bf16 MFMA (gemm.h SPLIT6; rt_core.hip)
 // A frame-resident forward (k_vision_fwd / k_vision_fwd_f32) can run on this layout.  The learner's
 // forward then stores no Xp, so the backward never trusts the Xp region's contents where this holds:
 // its layered launches rebuild the image from the observation (conv1_wgrad_frames).  Stated on the
@@ -226,30 +213,9 @@ bool f32_split6();   // fp32 path: large GEMMs as bf16x6 split products (rt_core
 inline bool vis_frames_layout(const Layout& L) {
   return vis_fits(L.H, L.W, L.H1, L.W1, L.h, L.w) && (L.dt == AAA_BF16 || f32_split6());
 }
-// An id of another family, or one this family holds for the other operand type only, runs tile 4
-// (every family has a 4).  < 0: the variable names an id that no family holds; the caller
-// refuses (tile_unknown).
-static int step_tile(long out_tiles32, const char* env, bool bptt, bool bf16 = false) {
-  const int v = env_int(env, -1);
-  if (v >= 0) {
-    const unsigned served = bptt ? tile_dt(BpttTiles{}, v) : tile_dt(FwdTiles{}, v);
-    return served & (bf16 ? kBf16 : kF32) ? v : (tile_known(v) ? 4 : -1);
-  }
-  // bf16 BPTT: 128x128 from ~3/4 of a workgroup per CU (C3: 242 WGs), else 128x64
-  // (tools/ubench/bf16_tiles at B=128: 34.6 vs 39.6 us)
-  // below that, 128x64 with a 4-way in-WG split-K (8 waves; C4: 50.0 vs 52.5 us for the 4-wave
-  // 2-way tile 8, tools/ab_bptt_bf16.sh)
-  if (bptt && bf16) return out_tiles32 >= 4L * 4 * 192 ? 7 : 22;
-  // fp32 (C2: 484 BPTT / 1936 forward tiles): 32x32 BK64 4-way BPTT on a 3-stage ring, two WGs
-  // per CU whose barriers are not in step (51.6 vs 54.4 us for 64x32 BK128, 54.6 vs 55.9 for
-  // 32x64); 64x64 BK64 forward 47.4 us (32x64 / 32x32 / 64x32 split-K rings: 52-55 us)
-  // (bench.py kernel table, tools/ab_bptt.sh)
-  // fp32 with f32_split6(): below 1024 tiles (the B=1 episode / actor: 68) the split-K
-  // split-product tile 31 (15.0 + 5.6 us per step vs 37 us for the fp32 tile 16 at the
-  // episode's 27x20 grid; C2 itself runs the frame-group BPTT, recur_bwd_f32.h)
-  if (bptt) return out_tiles32 < 1024 ? (f32_split6() ? 31 : 16) : (out_tiles32 < 1536 ? 1 : 0);
-  return out_tiles32 < 1024 ? 5 : 6;
-}
+// ... and this call may run one (AAA_VIS_FRAMES=0: the layered kernels, forward and backward)
+inline bool vis_frames_on(const Layout& L) { return vis_fits(L.H, L.W, L.H1, L.W1, L.h, L.w) && env_int("AAA_VIS_FRAMES", 1); }
+// A tile variable names an id that no family holds (RecurPlan's tiles < 0, fused_step): the launch site refuses
 static int tile_unknown(const char* env) {
   return fail(AAA_E_ARG, "%s %d: no such tile id (csrc/step_tiles.h)", env, env_int(env, -1));
 }
@@ -267,25 +233,31 @@ inline int splitk_slices(int K, int BK, int nsplit) {
   return (K + kc - 1) / kc;
 }
 
-// fp16 gate-activation storage (halves the step epilogues' largest stream):
-// bf16 operands, fused x-part (the gate buffer then holds activations only)
-// and a bf16 BPTT tile that reads them (step_tiles.h kG16).  AAA_GATES_F16=0 keeps fp32.  Forward and
-// backward evaluate this identically (same env, same shapes).
-// The x-part rides in the step GEMM for bf16 and for small steps (M = B*P
-// pixels; the actor's B = 1: one launch instead of two latency-bound ones);
-// fp32 at C2 (M = 3872) keeps the batched x-part (measured 5.02 vs 5.09 ms).
-// bf16 ConvLSTM forward on the frame-resident kernel (recur.h): one workgroup
-// per frame for the whole unroll, on grids whose images fit its LDS (84x84
-// frames), once the batch fills most of the chip's 256 CUs (C3, B=256: 55 vs
-// 79 us per step; C4's B=128 leaves half the CUs idle: 49 vs 43 us,
-// profiles/r02/frames).  AAA_FRAMES_FWD=1/0 forces it on/off.
-int frames_fwd(const Layout& L);
-static bool fused_x(int dt, int M) { return env_int("AAA_FUSED_X", dt == AAA_BF16 || M <= 1024 ? 1 : 0) != 0; }
-static bool gates_f16(int dt, int M) {
-  if (dt != AAA_BF16 || !fused_x(dt, M) || !ab_int("AAA_GATES_F16", 1)) return false;
-  const int bt = step_tile((long)(128 / 32) * ((M + 31) / 32), "AAA_BPTT_TILE", true, true);
-  return (tile_gates(BpttTiles{}, bt) & kG16) != 0;
-}
+// ------------------------------------------------------ recurrence plan --
+// How one call runs the ConvLSTM recurrence and how its state lies in the workspace: decided once per call from the
+// layout, the environment and the device (recur_plan, rt_core.hip: the rules and their measurements) and read by the
+// forward, the BPTT and the entries that describe the workspace, which therefore agree.  Nothing is kept between calls.
+enum class RecurFwd {
+  FramesF32,    // fp32 frame-group launch, fwd_g workgroups per frame (recur_f32.h)
+  BandBf16,     // bf16 band-mode frame-resident launch, fwd_g bands per frame (recur.h BAND)
+  FramesBf16,   // bf16 frame-resident launch, fwd_g = 1 or 2 workgroups per frame (recur.h)
+  FusedSteps,   // per step, x- and h-part in one GEMM
+  XpartSteps    // batched x-part, then the h-part per step
+};
+struct RecurPlan {
+  bool fused_x;             // the x-part rides in the step GEMM (AAA_FUSED_X)
+  int bwd_tile, fwd_tile;   // AAA_BPTT_TILE / AAA_STEP_TILE of the per-step chains (step_tiles.h); < 0: no such id
+  bool g16;                 // gate activations stored as fp16 (gate_bytes 2), else fp32 (4)
+  int gate_bytes;
+  RecurFwd fwd;             // the forward's path and its workgroups (bands) per frame, 0 for the per-step paths
+  int fwd_g;
+  int fb;                   // bf16 frame-resident BPTT: workgroups (bands) per frame, 0: the per-step chain
+  bool fb32;                // fp32 frame-group BPTT (G = 8)
+  int cqm;                  // recur.h kCqm* mask of the channel-quad-major Cst / Gt / dO slices; 0: all row-major
+};
+// resets: the call carries an episode-start mask (fp32), which not every frame-group kernel takes
+RecurPlan recur_plan(const Layout& L, bool resets);
+bool gates_f16(int dt, int M);   // the plan's g16 for the component cell entries, which have no Layout
 
 // One per-step ConvLSTM GEMM: D[Mi][M] = W[Mi][K] x im2col(src)[K][M] with
 // epilogue ep.  PIPE = LDS-DMA ring (glds.h; needs src already in T),
@@ -356,12 +328,12 @@ template <> struct DeepLd<LdRowsT> {
   template <typename G, typename T, int R, int BK, int NT> using type = LdRowsTN<G, T, R, BK, NT>;
   static bool fits(const void*, int ld, int nrows) { return ld % 4 == 0 && nrows % 4 == 0; }
 };
-constexpr int kTailStages = 8;
+constexpr int kTailStages = 8;   // K tiles of global loads in flight per workgroup (gemm_kernel_deep)
 #ifdef AAA_ABLATION
 constexpr bool kAblationBuild = true;
 #else
 constexpr bool kAblationBuild = false;
-#endif   // K tiles of global loads in flight per workgroup (gemm_kernel_deep)
+#endif
 
 // One operand of a tail GEMM: nrows rows of fp32 at pitch ld (all head_gemm / tail_gemm read of it).
 struct Rows {
@@ -577,14 +549,7 @@ static int fused_step(const T* WpXH, const T* xht, int h, int w, int M, const Ep
 }
 
 // ---------------------------------------------- frame-resident dispatch ----
-int device_cus();   // CUs of the current device
-// Workgroups per frame of the bf16 frame-resident kernels (0: per-step launches).
-int frames_g(const Layout& L, const char* env);
-int frames_band(const Layout& L);   // band mode (recur.h BAND): kRecBands, else 0
-int f32_frames(const Layout& L);    // fp32 frame-group G (recur_f32.h), else 0
-int frames_bwd(const Layout& L, bool g16);
-// Cst / Gt / dO slices channel-quad-major (recur.h cqm4): the frame-resident forward + BPTT pair
-int cqm_layout(const Layout& L);   // recur.h kCqm* mask of the channel-quad-major slices (0: all row-major)
+int device_cus();   // CUs of the current device (which frame kernel runs, and the slices' layout: RecurPlan)
 // h_t of all T*B frames as the attention readout reads it: the fp32 Hs slices
 // (fp32 path), or the h half of XH slots 1..T (bf16 path: no fp32 copy of h_t
 // is kept -- the readout reads the bf16 h the next step's conv and the weight
@@ -595,10 +560,29 @@ inline OSrc readout_h(const Layout& L, char* ws) {
   return o_f32((const float*)(ws + L.Hs));
 }
 int rec_stagger(const char* env);   // start offset of half the frames, 100-MHz ticks
-// fp32 path: its large GEMMs on the bf16 MFMA with three-way split operands (gemm.h SPLIT6)
-bool f32_split6();
 
 // ------------------------------------------------------- cross-unit paths --
+// What the phases of one forward / backward call share: the layout, the call's buffers, the caller's stream, (fp32)
+// the episode-start mask (T, B) or null, the recurrence's plan, and for the call's duration the tail GEMMs' arithmetic
+// (bf16 path: split operands on the bf16 MFMA, AAA_TAIL_SPLIT3=0: the fp32 MFMA) under the timer class tail_kind.
+struct CallCtx {
+  const Layout& L;
+  const aaa_io* io;
+  char* ws;
+  const char* pk;
+  const float* prm;
+  float* grads;   // (the backward's)
+  hipStream_t st;
+  const float* reset;
+  RecurPlan plan;
+  TailPrecision tail;
+  CallCtx(const Layout& l, const aaa_io* i, hipStream_t s, const float* r, int tail_kind)
+      : L(l), io(i), ws((char*)i->workspace), pk((const char*)i->packed), prm(i->params), grads(i->grads), st(s),
+        reset(r), plan(recur_plan(l, r != nullptr)),
+        tail(l.dt == AAA_BF16 && env_int("AAA_TAIL_SPLIT3", 1), l.dt == AAA_F32 && f32_split6(), tail_kind) {}
+  float* Wf(size_t off) const { return (float*)(ws + off); }
+  template <typename T> T* Wt(size_t off) const { return (T*)(ws + off); }
+};
 template <typename T> int pack_impl(const Layout& L, const float* prm, char* pk, hipStream_t st);
 template <typename T, typename OT>
 int vision_fwd(const Layout& L, int F, const char* pk, const float* prm, const void* frames, T* Xp, T* Y1, OT* out,

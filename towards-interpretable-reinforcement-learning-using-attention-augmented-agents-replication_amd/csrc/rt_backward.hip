@@ -457,7 +457,7 @@ static size_t vbwd_f32_room(const Layout& L, int F, size_t part_bytes) {
 template <typename T>
 static bool vbwd_on(const Layout& L, int F, size_t part_bytes = 0) {
   if constexpr (std::is_same<T, float>::value) {
-    return f32_split6() && L.fu8 && vbwd_f32_fits(L.H, L.W, L.H1, L.W1, L.h, L.w) && env_int("AAA_VIS_FRAMES", 1) &&
+    return f32_split6() && L.fu8 && vbwd_f32_fits(L.H, L.W, L.H1, L.W1, L.h, L.w) && vis_frames_on(L) &&
            env_int("AAA_VIS_BWD_FRAMES", 1) && F >= env_int("AAA_VBWD_MINF", 1) * device_cus() &&
            vbwd_f32_groups(F, device_cus(), vbwd_f32_room(L, F, part_bytes)) >= 1;
   } else if constexpr (!std::is_same<T, __bf16>::value) {
@@ -465,7 +465,7 @@ static bool vbwd_on(const Layout& L, int F, size_t part_bytes = 0) {
     return false;
   } else {
     if (!part_bytes) part_bytes = (size_t)F * L.P1 * 32 * L.esz;
-    return L.fu8 && vbwd_fits(L.H, L.W, L.H1, L.W1, L.h, L.w) && env_int("AAA_VIS_FRAMES", 1) &&
+    return L.fu8 && vbwd_fits(L.H, L.W, L.H1, L.W1, L.h, L.w) && vis_frames_on(L) &&
            env_int("AAA_VIS_BWD_FRAMES", 1) && F >= env_int("AAA_VBWD_MINF", 0) * device_cus() &&
            (size_t)vbwd_groups(F, device_cus()) * kVbPart * 4 <= part_bytes;
   }
@@ -529,20 +529,7 @@ int vision_bwd_alone(const Layout& L, const char* pk, const void* frames, const 
 }
 
 // ------------------------------------------------------------ backward ----
-// What the phases of one backward call share: the layout, the call's buffers, the caller's stream and
-// (fp32) the episode-start mask (T, B) or null.  Everything else a phase needs is an argument.
-struct BwdCtx {
-  const Layout& L;
-  const aaa_io* io;
-  char* ws;
-  const char* pk;
-  const float* prm;
-  float* grads;
-  hipStream_t st;
-  const float* reset;
-  float* Wf(size_t off) const { return (float*)(ws + off); }
-  template <typename T> T* Wt(size_t off) const { return (T*)(ws + off); }
-};
+// (what the phases of one backward call share: rt.h CallCtx)
 
 // The tail's backward GEMMs.  dgrad: D[Mi][Nj] = Wt^T[Mi][K] x dY[Nj][K]^T through ``ep`` (Wt: the
 // weight as stored, K rows of Mi).  wgrad: out[Mi][Nj] += dA^T x X over the F frames (Mi, Nj: the
@@ -557,26 +544,27 @@ static hipError_t tail_wgrad(const Rows& dA, const Rows& X, float* out, int ldo,
                                      wgrad_splits(cdiv(Mi, 64) * cdiv(Nj, 64), F, CF::BK), st);
 }
 // The tail's packed gradients into the reference's tensors (stateful: W_hh's too)
-static hipError_t tail_unpack(const Layout& L, char* ws, float* grads, bool stateful, hipStream_t st) {
-  auto Wf = [&](size_t off) { return (float*)(ws + off); };
+static hipError_t tail_unpack(const CallCtx& c, bool stateful) {
+  const Layout& L = c.L;
+  float* grads = c.grads;
   F32Unpack up;
-  up.gW1p = Wf(L.gW1p); up.gWihp = Wf(L.gWihp); up.gblc = Wf(L.gblc); up.gWhd = Wf(L.gWhd); up.gbhd = Wf(L.gbhd);
+  up.gW1p = c.Wf(L.gW1p); up.gWihp = c.Wf(L.gWihp); up.gblc = c.Wf(L.gblc); up.gWhd = c.Wf(L.gWhd); up.gbhd = c.Wf(L.gbhd);
   up.a0w = grads + L.poff[A0W]; up.wih = grads + L.poff[WIH]; up.bih = grads + L.poff[BIH];
   up.bhh = grads + L.poff[BHH]; up.pw = grads + L.poff[PW]; up.vw = grads + L.poff[VW];
   up.pb = grads + L.poff[PB]; up.vb = grads + L.poff[VB];
   up.ans_in = L.ans_in; up.ans_ld = L.ans_ld; up.A = L.A;
   if (stateful) {
-    up.gWihhp = Wf(L.gWihhp);
+    up.gWihhp = c.Wf(L.gWihhp);
     up.whh = grads + L.poff[WHH];
   }
-  return unpack_f32(up, st);
+  return unpack_f32(up, c.st);
 }
 
 // Stateful policy core, backward of the tail (phase HEAD): the dgrad chain runs
 // step by step from t = T-1 (the carries dh, dc of the core state flow through
 // the LSTMCell's W_hh and the query MLP into step t-1); every weight gradient
 // is then one batched GEMM over all frames from the saved per-step operands.
-static int head_backward_stateful(const BwdCtx& c) {
+static int head_backward_stateful(const CallCtx& c) {
   const Layout& L = c.L;
   const aaa_io* io = c.io;
   const hipStream_t st = c.st;
@@ -616,7 +604,7 @@ static int head_backward_stateful(const BwdCtx& c) {
     {
       TimerScope tim(AAA_TIMER_ATTN_BWD, st, (double)B * attn_bwd_bytes(P, L.nq, L.esz), "k_attn_bwd, per-frame query (stateful core)");
       HIPCHK(attn_bwd(readout_h(L, c.ws).frame(f0, P), io->basis, c.Wf(L.Qf) + f0 * qd, c.Wf(L.Am) + f0 * P * L.nq, dAns,
-                      da, B, P, L.nq, c.Wf(L.dO) + f0 * P * 128, dQf, st, qd, 1, (cqm_layout(L) & kCqmDO) != 0));
+                      da, B, P, L.nq, c.Wf(L.dO) + f0 * P * 128, dQf, st, qd, 1, (c.plan.cqm & kCqmDO) != 0));
     }
     // query MLP backward to its input h_{t-1}
     HIPCHK(tail_dgrad({prm + L.poff[Q4W], qd, qd}, {dQf, qd, B},
@@ -649,7 +637,7 @@ static int head_backward_stateful(const BwdCtx& c) {
   HIPCHK(tail_wgrad({c.Wf(L.dq1s), 128, 128}, reset ? Rows{AOX + 256, 512, 256} : Rows{CH, 256, 256},
                     grads + L.poff[Q0W], 256, F, st));
   HIPCHK(colsum(c.Wf(L.dq1s), 128, F, 128, grads + L.poff[Q0B], st));
-  HIPCHK(tail_unpack(L, c.ws, grads, true, st));
+  HIPCHK(tail_unpack(c, true));
   return AAA_OK;
 }
 
@@ -660,7 +648,7 @@ static int head_backward_stateful(const BwdCtx& c) {
 // Below ~2048 frames the GEMMs are too short for the overlap to pay for the second queue's dispatch
 // cost on the rest of the step (C2, 640 frames: tail bwd -20 us but the step +10-15 us;
 // profiles/r06/ab/side/): one stream there.
-static int head_backward_zero_state(const BwdCtx& c) {
+static int head_backward_zero_state(const CallCtx& c) {
   const Layout& L = c.L;
   const hipStream_t st = c.st;
   const float* prm = c.prm;
@@ -699,7 +687,7 @@ static int head_backward_zero_state(const BwdCtx& c) {
   {
     TimerScope tim(AAA_TIMER_ATTN_BWD, st, (double)F * attn_bwd_bytes(P, L.nq, L.esz), "k_attn_bwd, 1 WG per frame");
     HIPCHK(attn_bwd(readout_h(L, c.ws), c.io->basis, (const float*)(c.pk + L.k_Q), c.Wf(L.Am), c.Wf(L.dAns), L.da, F, P,
-                    L.nq, c.Wf(L.dO), c.Wf(L.dQp), st, 0, 0, (cqm_layout(L) & kCqmDO) != 0));
+                    L.nq, c.Wf(L.dO), c.Wf(L.dQp), st, 0, 0, (c.plan.cqm & kCqmDO) != 0));
   }
   tail.reset(new TimerScope(AAA_TIMER_TAIL_BWD, st, 0.0, "bias column sums, query MLP backward, grad unpack"));
   {  // the bias grads of the heads, the LSTMCell and both answer layers, and dQ summed over frames: one launch
@@ -715,13 +703,13 @@ static int head_backward_zero_state(const BwdCtx& c) {
                    prm + L.poff[Q4W], (const float*)(c.pk + L.k_q1), (const float*)(c.pk + L.k_q2), grads + L.poff[Q4W],
                    grads + L.poff[Q4B], grads + L.poff[Q2W], grads + L.poff[Q2B], grads + L.poff[Q0B], st));
   if (ss) HIPCHK(stream_order(ss, st));   // join: the weight gradients
-  HIPCHK(tail_unpack(L, c.ws, grads, false, st));
+  HIPCHK(tail_unpack(c, false));
   return AAA_OK;
 }
 
 // Phase HEAD: zero the gradients and accumulators, concatenate the cotangents, then the tail's backward.
 template <typename T>
-static int head_backward(const BwdCtx& c) {
+static int head_backward(const CallCtx& c) {
   const Layout& L = c.L;
   {
     TimerScope tim(AAA_TIMER_MISC, c.st, 0.0, "grad/accumulator memsets, cotangent concat");
@@ -738,7 +726,7 @@ static int head_backward(const BwdCtx& c) {
 // dispatch of the VISION phase on its own (vision_bwd_alone), on this chunk's frames (a chunk is at most
 // L.fchunk frames: one pass of its loop)
 template <typename T>
-static int chunk_vision(const BwdCtx& c, int lo, int hi, hipStream_t vs) {
+static int chunk_vision(const CallCtx& c, int lo, int hi, hipStream_t vs) {
   const Layout& L = c.L;
   const int F1 = (hi - lo) * L.B;
   const size_t f0 = (size_t)lo * L.B;
@@ -758,7 +746,7 @@ static int chunk_vision(const BwdCtx& c, int lo, int hi, hipStream_t vs) {
 // dx_t (conv2's output gradient dY2) of steps [lo, hi) in one launch on ``s``:
 // D[64][rows] = WdT[0:64] * gather(dZ), conv2's bias gradient summed in the epilogue
 template <typename T>
-static int batched_dx(const BwdCtx& c, int lo, int hi, hipStream_t s) {
+static int batched_dx(const CallCtx& c, int lo, int hi, hipStream_t s) {
   const Layout& L = c.L;
   const int M = L.B * L.P, rows = (hi - lo) * M;
   const T* dz = c.Wt<T>(L.dZ) + (size_t)lo * M * 512;
@@ -863,7 +851,7 @@ static int batched_dx(const BwdCtx& c, int lo, int hi, hipStream_t s) {
 // (vision_here) -- the conv2/conv1 backward of those frames.  Every gradient accumulates atomically
 // into zeroed buffers, so chunks may run in any order.
 template <typename T>
-static int core_chunk(const BwdCtx& c, int lo, int hi, hipStream_t s, bool dx_fused, bool vision_here) {
+static int core_chunk(const CallCtx& c, int lo, int hi, hipStream_t s, bool dx_fused, bool vision_here) {
   const Layout& L = c.L;
   const int M = L.B * L.P, rows = (hi - lo) * M;
   // (the layered vision backward on the side stream beside the ConvLSTM weight gradient, ablation
@@ -903,7 +891,7 @@ struct BpttChain {
 // k_reset_gate_bwd rewrites the rows of step t-1's gate backward that an episode start at t or
 // t-1 changes.  Called after the gate backward of step t-1 (t = T: the last step's).
 template <typename T>
-static int bptt_fix(const BwdCtx& c, int t) {
+static int bptt_fix(const CallCtx& c, int t) {
   if (!c.reset) return AAA_OK;
   if constexpr (std::is_same<T, float>::value) {
     const Layout& L = c.L;
@@ -920,7 +908,7 @@ static int bptt_fix(const BwdCtx& c, int t) {
 
 // The gate backward of the last step (dh_T from io->dhT), which starts the per-step and frame-group chains
 template <typename T>
-static int bptt_last_gates(const BwdCtx& c, const BpttChain& ch) {
+static int bptt_last_gates(const CallCtx& c, const BpttChain& ch) {
   const Layout& L = c.L;
   const int M = L.B * L.P, t1 = L.T - 1;
   float* part = ch.part ? ch.part + (size_t)t1 * cdiv(M, ch.bj) * 512 : nullptr;
@@ -939,87 +927,76 @@ static int bptt_last_gates(const BwdCtx& c, const BpttChain& ch) {
 
 // bf16: the whole chain in one frame-resident launch (fb workgroups per frame), dx (dY2) and conv2's bias
 // gradient included
-template <typename T>
-static int bptt_frames_bf16(const BwdCtx& c, int fb) {
-  if constexpr (std::is_same<T, float>::value) {
-    return fail(AAA_E_ARG, "the frame-resident BPTT is bf16 only");
-  } else {
-    const Layout& L = c.L;
-    const aaa_io* io = c.io;
-    const int M = L.B * L.P;
-    RecBwdParams rp{(const __bf16*)(c.pk + L.k_Wbf), c.Wf(L.dO), (const _Float16*)(c.ws + L.Gt), c.Wf(L.Cst), io->dhT,
-                    c.Wf(L.dC), c.Wt<T>(L.dZ), c.Wf(L.dZp), io->dh0, c.Wt<T>(L.dY2), c.Wf(L.dxb),
-                    (int*)(c.ws + L.rflags), L.T, L.B, L.h, L.w, L.P, nullptr, pair_budget(L.T),
-                    rec_stagger("AAA_REC_STAGGER_BWD"), cqm_layout(L)};
-    // single-workgroup and paired kernels: row-padded images (recur_bwd.h kBwIBP) where they fit
-    // (C3 LDS bank conflicts 52.8 -> 10.0 %: profiles/r04/ab/rowpad_c3/); AAA_BW_ROWPAD=0 (A/B): 272-B rows only
-    rp.rowpad = fb <= 2 && ab_int("AAA_BW_ROWPAD", 1) ? bw_rowpad(L.h, L.w) : 0;
-    rp.sc1_all = ab_int("AAA_BW_SC1_ALL", 0);   // band kernel (A/B): sc1 for every dZ row, as in round 4
-    // single-workgroup kernel: the epilogue's inputs by LDS-DMA into a counted ring (recur_bwd.h RING)
-    rp.ring = fb == 1 && ab_int("AAA_BW_RING", 0);   // measured slower: ablation builds only
-    if (fb >= 2)   // paired or band mode: hand-off flags [B][fb]
-      if (const int rc = report_word("paired-kernel", &rp.report)) return rc;
-    {
-      // work: the h rows over T-1 steps (+ dh0) and the dx rows over all T (the batched dx it replaces)
-      TimerScope tim(AAA_TIMER_BPTT_STEP, c.st, 2.0 * M * 4608 * (128.0 * (L.T - 1 + (io->dh0 ? 1 : 0)) + 64.0 * L.T),
-                     fb == kRecBands && !rec_fits(L.h, L.w)
-                         ? strf("bf16 band-mode frame-resident BPTT + dx, %d steps per launch, %d bands per frame, "
-                                "fp16 gates [kernel: k_convlstm_bwd_frames<0, true]", L.T, fb)
-                         : strf("bf16 frame-resident BPTT + dx, %d steps per launch, %d WG per frame, fp16 gates "
-                                "[kernel: %s]", L.T, fb, fb == 2 ? "k_convlstm_bwd_pairs" : (rp.ring ? "k_convlstm_bwd_frames<ring>" : "k_convlstm_bwd_frames<0, false")));
-      HIPCHK(fb == 2 ? convlstm_bwd_pairs(rp, c.st) : (fb == 1 ? convlstm_bwd_frames(rp, c.st) : convlstm_bwd_band(rp, c.st)));
-    }
-    HIPCHK(colsum<float>(c.Wf(L.dxb), 64, L.B, 64, c.grads + L.poff[C1B], c.st));
-    return AAA_OK;
+static int bptt_frames_bf16(const CallCtx& c, int fb) {
+  const Layout& L = c.L;
+  const aaa_io* io = c.io;
+  const int M = L.B * L.P;
+  RecBwdParams rp{(const __bf16*)(c.pk + L.k_Wbf), c.Wf(L.dO), (const _Float16*)(c.ws + L.Gt), c.Wf(L.Cst), io->dhT,
+                  c.Wf(L.dC), c.Wt<__bf16>(L.dZ), c.Wf(L.dZp), io->dh0, c.Wt<__bf16>(L.dY2), c.Wf(L.dxb),
+                  (int*)(c.ws + L.rflags), L.T, L.B, L.h, L.w, L.P, nullptr, pair_budget(L.T),
+                  rec_stagger("AAA_REC_STAGGER_BWD"), c.plan.cqm};
+  // single-workgroup and paired kernels: row-padded images (recur_bwd.h kBwIBP) where they fit
+  // (C3 LDS bank conflicts 52.8 -> 10.0 %: profiles/r04/ab/rowpad_c3/); AAA_BW_ROWPAD=0 (A/B): 272-B rows only
+  rp.rowpad = fb <= 2 && ab_int("AAA_BW_ROWPAD", 1) ? bw_rowpad(L.h, L.w) : 0;
+  rp.sc1_all = ab_int("AAA_BW_SC1_ALL", 0);   // band kernel (A/B): sc1 for every dZ row, as in round 4
+  // single-workgroup kernel: the epilogue's inputs by LDS-DMA into a counted ring (recur_bwd.h RING)
+  rp.ring = fb == 1 && ab_int("AAA_BW_RING", 0);   // measured slower: ablation builds only
+  if (fb >= 2)   // paired or band mode: hand-off flags [B][fb]
+    if (const int rc = report_word("paired-kernel", &rp.report)) return rc;
+  {
+    // work: the h rows over T-1 steps (+ dh0) and the dx rows over all T (the batched dx it replaces)
+    TimerScope tim(AAA_TIMER_BPTT_STEP, c.st, 2.0 * M * 4608 * (128.0 * (L.T - 1 + (io->dh0 ? 1 : 0)) + 64.0 * L.T),
+                   fb == kRecBands && !rec_fits(L.h, L.w)
+                       ? strf("bf16 band-mode frame-resident BPTT + dx, %d steps per launch, %d bands per frame, "
+                              "fp16 gates [kernel: k_convlstm_bwd_frames<0, true]", L.T, fb)
+                       : strf("bf16 frame-resident BPTT + dx, %d steps per launch, %d WG per frame, fp16 gates "
+                              "[kernel: %s]", L.T, fb, fb == 2 ? "k_convlstm_bwd_pairs" : (rp.ring ? "k_convlstm_bwd_frames<ring>" : "k_convlstm_bwd_frames<0, false")));
+    HIPCHK(fb == 2 ? convlstm_bwd_pairs(rp, c.st) : (fb == 1 ? convlstm_bwd_frames(rp, c.st) : convlstm_bwd_band(rp, c.st)));
   }
+  HIPCHK(colsum<float>(c.Wf(L.dxb), 64, L.B, 64, c.grads + L.poff[C1B], c.st));
+  return AAA_OK;
 }
 
 // fp32: the frame-group BPTT (recur_bwd_f32.h, G = 8) behind the forward's frame-group kernel, one launch for
 // the dh chain of all steps.  *dx_fused <- with split products it computed dx (dY2) and conv2's bias gradient too.
-template <typename T>
-static int bptt_frames_f32(const BwdCtx& c, bool* dx_fused) {
-  if constexpr (!std::is_same<T, float>::value) {
-    return fail(AAA_E_ARG, "the frame-group BPTT is fp32 only");
-  } else {
-    const Layout& L = c.L;
-    const aaa_io* io = c.io;
-    const int M = L.B * L.P;
-    int* rep = nullptr;
-    if (const int rc = report_word("frame-group", &rep)) return rc;
-    RecBwdF32Params rp{(const float*)(c.pk + L.k_Wb32), c.Wf(L.dO), c.Wf(L.Gt), c.Wf(L.Cst), c.Wf(L.dC), c.Wf(L.dZ),
-                       c.Wf(L.dZp), io->dh0, c.Wf(L.xpart), (int*)(c.ws + L.rflags), rep, pair_budget(L.T),
-                       L.T, L.B, L.h, L.w, L.P, {}};
-    const bool s6 = f32_split6();
-    rp.reset = c.reset;
-    rp.Wb6 = (const u32x2*)(c.pk + L.k_Wb6);
-    if (s6) {   // dx fused (DX): conv2's output gradient and its bias partials from the same K loop
-      rp.Wx6 = (const u32x2*)(c.pk + L.k_Wx6);
-      rp.Wb6p = (const u32x4*)(c.pk + L.k_Wb6p);
-      rp.Wx6p = (const u32x4*)(c.pk + L.k_Wx6p);
-      rp.dx = c.Wf(L.dY2);
-      rp.dxb = c.Wf(L.dxb);
-    }
-    {
-      // work: the dh rows over T-1 steps (+ dh0), and with dx fused the dx rows over all T steps (the
-      // batched dx it replaces) plus the dh rows of step 0 that the extra iteration computes
-      const double dh_steps = L.T - 1 + ((io->dh0 || s6) ? 1 : 0);
-      TimerScope tim(AAA_TIMER_BPTT_STEP, c.st, 2.0 * M * 4608 * (128.0 * dh_steps + (s6 ? 64.0 * L.T : 0.0)),
-                     s6 ? strf("fp32 frame-group BPTT + dx (bf16x6 split products), %d steps per launch, 8 WG "
-                               "per frame [kernel: k_convlstm_bwd_f32]%s", L.T, c.reset ? ", resets" : "")
-                        : strf("fp32 frame-group BPTT (dh rows), %d steps per launch, 8 WG per frame "
-                               "[kernel: k_convlstm_bwd_f32]", L.T));
-      HIPCHK(convlstm_bwd_f32(rp, c.st, s6));
-    }
-    if (s6) HIPCHK(colsum<float>(c.Wf(L.dxb), 64, L.B, 64, c.grads + L.poff[C1B], c.st));
-    *dx_fused = s6;
-    return AAA_OK;
+static int bptt_frames_f32(const CallCtx& c, bool* dx_fused) {
+  const Layout& L = c.L;
+  const aaa_io* io = c.io;
+  const int M = L.B * L.P;
+  int* rep = nullptr;
+  if (const int rc = report_word("frame-group", &rep)) return rc;
+  RecBwdF32Params rp{(const float*)(c.pk + L.k_Wb32), c.Wf(L.dO), c.Wf(L.Gt), c.Wf(L.Cst), c.Wf(L.dC), c.Wf(L.dZ), c.Wf(L.dZp),
+                     io->dh0, c.Wf(L.xpart), (int*)(c.ws + L.rflags), rep, pair_budget(L.T), L.T, L.B, L.h, L.w, L.P, {}};
+  const bool s6 = f32_split6();
+  rp.reset = c.reset;
+  rp.Wb6 = (const u32x2*)(c.pk + L.k_Wb6);
+  if (s6) {   // dx fused (DX): conv2's output gradient and its bias partials from the same K loop
+    rp.Wx6 = (const u32x2*)(c.pk + L.k_Wx6);
+    rp.Wb6p = (const u32x4*)(c.pk + L.k_Wb6p);
+    rp.Wx6p = (const u32x4*)(c.pk + L.k_Wx6p);
+    rp.dx = c.Wf(L.dY2);
+    rp.dxb = c.Wf(L.dxb);
   }
+  {
+    // work: the dh rows over T-1 steps (+ dh0), and with dx fused the dx rows over all T steps (the
+    // batched dx it replaces) plus the dh rows of step 0 that the extra iteration computes
+    const double dh_steps = L.T - 1 + ((io->dh0 || s6) ? 1 : 0);
+    TimerScope tim(AAA_TIMER_BPTT_STEP, c.st, 2.0 * M * 4608 * (128.0 * dh_steps + (s6 ? 64.0 * L.T : 0.0)),
+                   s6 ? strf("fp32 frame-group BPTT + dx (bf16x6 split products), %d steps per launch, 8 WG "
+                             "per frame [kernel: k_convlstm_bwd_f32]%s", L.T, c.reset ? ", resets" : "")
+                      : strf("fp32 frame-group BPTT (dh rows), %d steps per launch, 8 WG per frame "
+                             "[kernel: k_convlstm_bwd_f32]", L.T));
+    HIPCHK(convlstm_bwd_f32(rp, c.st, s6));
+  }
+  if (s6) HIPCHK(colsum<float>(c.Wf(L.dxb), 64, L.B, 64, c.grads + L.poff[C1B], c.st));
+  *dx_fused = s6;
+  return AAA_OK;
 }
 
 // One step of the per-step chain: dh_{t-1} = WdT[64:192] x gather(dZ_t) with the gate backward of step t-1 as
 // the GEMM's epilogue (t = 0: dh0 out), then the episode-start rewrite of that step's rows
 template <typename T>
-static int bptt_step(const BwdCtx& c, const BpttChain& ch, int t) {
+static int bptt_step(const CallCtx& c, const BpttChain& ch, int t) {
   const Layout& L = c.L;
   const int M = L.B * L.P, ntj = cdiv(M, ch.bj);
   const bool prev = t > 0;
@@ -1076,7 +1053,7 @@ static int bptt_step(const BwdCtx& c, const BpttChain& ch, int t) {
 // each chunk's frames too).  deferred_unpack: null, or where to leave the ConvLSTM grads' reference tensors
 // for the VISION phase of this call, whose launch then unpacks them with the vision grads.
 template <typename T>
-static int core_backward(const BwdCtx& c, int phases, LstmGrads* deferred_unpack) {
+static int core_backward(const CallCtx& c, int phases, LstmGrads* deferred_unpack) {
   const Layout& L = c.L;
   const aaa_io* io = c.io;
   const hipStream_t st = c.st;
@@ -1094,7 +1071,7 @@ static int core_backward(const BwdCtx& c, int phases, LstmGrads* deferred_unpack
     HIPCHK(prologue<T>(z, 0, nullptr, (T*)nullptr, 0, 0, 1, nullptr, nullptr, nullptr, st));
     if (io->dcT) HIPCHK(hipMemcpyAsync(c.Wf(L.dC), io->dcT, (size_t)M * 128 * 4, hipMemcpyDeviceToDevice, st));
   }
-  const int bwd_tile = step_tile((long)(128 / 32) * cdiv(M, 32), "AAA_BPTT_TILE", true, L.dt == AAA_BF16);
+  const int bwd_tile = c.plan.bwd_tile;
   if (bwd_tile < 0) return tile_unknown("AAA_BPTT_TILE");
   BpttChain ch = for_tile<BpttTiles>(bwd_tile, BpttChain{}, [bwd_tile](auto tile) {
     using Tl = decltype(tile);
@@ -1104,12 +1081,9 @@ static int core_backward(const BwdCtx& c, int phases, LstmGrads* deferred_unpack
   const bool fixk = ch.split == SplitK::SliceFix;   // split-K finished in the GEMM: bias from dZ's column sum
   if (fixk && L.dhs)   // the fixup counters (self-resetting; zeroed per call in case a launch was abandoned)
     HIPCHK(hipMemsetAsync(c.ws + L.dhs + (size_t)std::max(kBpttSplitMax * 128, 4 * 512) * M * 4, 0, 4096, st));
-  ch.g16 = gates_f16(L.dt, M);
-  const int fb = frames_bwd(L, ch.g16);   // bf16: workgroups per frame of the frame-resident launch, 0: none
-  // (a mask: the frame-group BPTT's RST variant, the production split-product kernel with dx fused; else the
-  // per-step chain)
-  const bool fb32 = std::is_same<T, float>::value && (!c.reset || f32_split6()) && f32_frames(L) == 8 &&
-                    env_int("AAA_F32_FRAMES_BWD", 1);
+  ch.g16 = c.plan.g16;
+  const int fb = c.plan.fb;   // bf16: workgroups per frame of the frame-resident launch, 0: none
+  const bool fb32 = c.plan.fb32;   // fp32: the frame-group launch (a mask: its RST variant, with dx fused)
   // Gate-bias partials from the step kernels' epilogues: ring tiles only; not where the frame-group kernel
   // writes its own per-(step, frame) partials (step T-1's included); not under a mask, where the gate-bias
   // gradient is the column sum of the final dZ, not of partials taken before bptt_fix's rewrite.
@@ -1118,11 +1092,12 @@ static int core_backward(const BwdCtx& c, int phases, LstmGrads* deferred_unpack
     if (const int rc = bptt_last_gates<T>(c, ch)) return rc;
   misc.reset();
   bool dx_fused = false;   // the BPTT launch computed dx (dY2) and conv2's bias gradient itself
-  if (fb) {
-    if (const int rc = bptt_frames_bf16<T>(c, fb)) return rc;
+  if constexpr (std::is_same<T, float>::value) {
+    if (fb32)
+      if (const int rc = bptt_frames_f32(c, &dx_fused)) return rc;
+  } else if (fb) {
+    if (const int rc = bptt_frames_bf16(c, fb)) return rc;
     dx_fused = true;
-  } else if (fb32) {
-    if (const int rc = bptt_frames_f32<T>(c, &dx_fused)) return rc;
   }
   int done_hi = L.T;   // chunks [lo, done_hi) not yet issued
   auto flush = [&](int ready_lo) -> int {   // dz of steps >= ready_lo are final
@@ -1167,7 +1142,7 @@ static int core_backward(const BwdCtx& c, int phases, LstmGrads* deferred_unpack
 // Phase VISION: the conv2 / conv1 backward over all frames unless CORE ran it chunk by chunk in this call
 // (then core_unpack holds the ConvLSTM grads' reference tensors), and the unpack of the packed gradients.
 template <typename T>
-static int vision_backward(const BwdCtx& c, int phases, const LstmGrads& core_unpack) {
+static int vision_backward(const CallCtx& c, int phases, const LstmGrads& core_unpack) {
   const Layout& L = c.L;
   const bool vision_here = (phases & AAA_BWD_CORE) != 0;   // done with the CORE phase's chunks
   TimerScope tim(AAA_TIMER_VISION_BWD, c.st, vision_here ? 0.0 : (double)L.F * vision_bwd_flop(L),
@@ -1187,10 +1162,7 @@ static int vision_backward(const BwdCtx& c, int phases, const LstmGrads& core_un
 
 template <typename T>
 int backward_impl(const Layout& L, const aaa_io* io, int phases, hipStream_t st, const float* reset) {
-  // bf16 path: the fp32 tail GEMMs on the bf16 MFMA with split operands (AAA_TAIL_SPLIT3=0: fp32 MFMA)
-  TailPrecision tail_prec(std::is_same<T, __bf16>::value && env_int("AAA_TAIL_SPLIT3", 1),
-                          std::is_same<T, float>::value && f32_split6(), AAA_TIMER_TAIL_BWD);
-  const BwdCtx c{L, io, (char*)io->workspace, (const char*)io->packed, io->params, io->grads, st, reset};
+  const CallCtx c(L, io, st, reset, AAA_TIMER_TAIL_BWD);
   const bool vision = (phases & AAA_BWD_VISION) != 0;
   LstmGrads core_unpack{};   // the ConvLSTM grads' reference tensors, unpacked with the vision grads when both run here
   if (phases & AAA_BWD_HEAD)

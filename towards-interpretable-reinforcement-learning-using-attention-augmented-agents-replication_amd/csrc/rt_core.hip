@@ -416,19 +416,18 @@ int device_cus() {   // per device ordinal, queried once
 // occupy at least a quarter of the slots; else the per-step kernels.
 // AAA_FRAMES_FWD / AAA_FRAMES_BWD = 0 / 1 / 2 force it.
 static_assert(2 * kBwIBS + 4 * 16 * 64 * 16 > 160 * 1024 / 2, "one frame-resident workgroup per CU");
-int frames_g(const Layout& L, const char* env) {
+static int frames_g(const Layout& L, const char* env) {
   if (L.dt != AAA_BF16 || !rec_fits(L.h, L.w)) return 0;
   const int slots = device_cus();
   const int v = env_int(env, 8 * L.B >= 5 * slots ? 1 : (8 * L.B >= slots && 2 * L.B <= slots ? 2 : 0));
   return v == 1 ? 1 : (v == 2 && 2 * L.B <= slots ? 2 : 0);
 }
-int frames_fwd(const Layout& L) { return frames_g(L, "AAA_FRAMES_FWD"); }
 // bf16 forward on the band-mode frame-resident kernel (recur.h BAND): grids too
 // large for one workgroup's images (168x168 frames: 21x21) split into kRecBands
 // row bands, one workgroup each, when B * kRecBands workgroups fit one
 // residency wave (config 5: B = 64 per GPU -> 256).  AAA_FRAMES_BAND = 0 keeps
 // the per-step launches.
-int frames_band(const Layout& L) {
+static int frames_band(const Layout& L) {
   if (L.dt != AAA_BF16 || rec_fits(L.h, L.w) || !rec_band_fits(L.h, L.w) || !env_int("AAA_FRAMES_BAND", 1)) return 0;
   return 8 * kRecBands * ((L.B + 7) / 8) <= device_cus() ? kRecBands : 0;
 }
@@ -436,7 +435,7 @@ int frames_band(const Layout& L) {
 // per frame for all T steps, once B * G fills at least half the CUs in one
 // residency wave (C2: B = 32, G = 8 on 256 CUs).  AAA_F32_FRAMES = 0 keeps the
 // per-step launches (A/B and parity of both paths); 8 / 4 force that G.
-int f32_frames(const Layout& L) {
+static int f32_frames(const Layout& L) {
   if (L.dt != AAA_F32 || !f32_rec_fits(L.h, L.w)) return 0;
   const int v = env_int("AAA_F32_FRAMES", 1), cus = device_cus();
   if (v == 8 || v == 4) return f32_grid(L.B, v) <= cus ? v : 0;   // forced G (tests, A/B)
@@ -444,24 +443,76 @@ int f32_frames(const Layout& L) {
   const int G = f32_rec_g(L.B, cus);
   return G && 2 * G * L.B >= cus ? G : 0;
 }
-// The BPTT chain on the frame-resident kernels (recur_bwd.h; fp16 gate storage):
-// workgroups per frame as the forward's (AAA_FRAMES_BWD = 0 / 1 / 2 forces it).
 // Start offset of half the frames of the bf16 frame-resident kernels (common.h
 // stagger_wait), in microseconds -> 100-MHz ticks.
 int rec_stagger(const char* env) { return 100 * ab_int(env, 0); }
 // default on: C2 150.6k -> 175.6k frames/s (profiles/r04/ab_split6); AAA_F32_SPLIT6=0 restores the fp32 MFMA
 bool f32_split6() { return env_int("AAA_F32_SPLIT6", 1) != 0; }
-// Band mode (recur_bwd.h BAND) wherever the forward runs in band mode: kRecBands.
-// Only behind a frame-resident forward: the two share the channel-quad-major
-// slices of Cst / Gt / dO (cqm_layout), which the per-step kernels do not read.
-int frames_bwd(const Layout& L, bool g16) {
-  if (!g16) return 0;
-  if (const int nb = frames_band(L)) return bw_band_fits(L.h, L.w) ? nb : 0;
-  return frames_fwd(L) ? frames_g(L, "AAA_FRAMES_BWD") : 0;
+// Step-kernel tile choice (env AAA_STEP_TILE / AAA_BPTT_TILE override; the ids: step_tiles.h).  The default
+// picks by how many 32x32 output tiles the step has, i.e. how many waves it can feed; measured on C2.
+// An id of another family, or one this family holds for the other operand type only, runs tile 4 (every family
+// has a 4).  < 0: the variable names an id that no family holds; the caller refuses (tile_unknown).
+static int step_tile(long out_tiles32, const char* env, bool bptt, bool bf16 = false) {
+  const int v = env_int(env, -1);
+  if (v >= 0) {
+    const unsigned served = bptt ? tile_dt(BpttTiles{}, v) : tile_dt(FwdTiles{}, v);
+    return served & (bf16 ? kBf16 : kF32) ? v : (tile_known(v) ? 4 : -1);
+  }
+  // bf16 BPTT: 128x128 from ~3/4 of a workgroup per CU (C3: 242 WGs), else 128x64
+  // (tools/ubench/bf16_tiles at B=128: 34.6 vs 39.6 us)
+  // below that, 128x64 with a 4-way in-WG split-K (8 waves; C4: 50.0 vs 52.5 us for the 4-wave
+  // 2-way tile 8, tools/ab_bptt_bf16.sh)
+  if (bptt && bf16) return out_tiles32 >= 4L * 4 * 192 ? 7 : 22;
+  // fp32 (C2: 484 BPTT / 1936 forward tiles): 32x32 BK64 4-way BPTT on a 3-stage ring, two WGs
+  // per CU whose barriers are not in step (51.6 vs 54.4 us for 64x32 BK128, 54.6 vs 55.9 for
+  // 32x64); 64x64 BK64 forward 47.4 us (32x64 / 32x32 / 64x32 split-K rings: 52-55 us)
+  // (bench.py kernel table, tools/ab_bptt.sh)
+  // fp32 with f32_split6(): below 1024 tiles (the B=1 episode / actor: 68) the split-K
+  // split-product tile 31 (15.0 + 5.6 us per step vs 37 us for the fp32 tile 16 at the
+  // episode's 27x20 grid; C2 itself runs the frame-group BPTT, recur_bwd_f32.h)
+  if (bptt) return out_tiles32 < 1024 ? (f32_split6() ? 31 : 16) : (out_tiles32 < 1536 ? 1 : 0);
+  return out_tiles32 < 1024 ? 5 : 6;
 }
-int cqm_layout(const Layout& L) {
+// The x-part rides in the step GEMM for bf16 and for small steps (M = B*P pixels; the actor's B = 1: one
+// launch instead of two latency-bound ones); fp32 at C2 (M = 3872) keeps the batched x-part (measured 5.02
+// vs 5.09 ms).
+static bool fused_x(int dt, int M) { return env_int("AAA_FUSED_X", dt == AAA_BF16 || M <= 1024 ? 1 : 0) != 0; }
+// fp16 gate-activation storage (halves the step epilogues' largest stream): bf16 operands, fused x-part (the
+// gate buffer then holds activations only) and a bf16 BPTT tile that reads them (step_tiles.h kG16).
+// AAA_GATES_F16=0 keeps fp32.
+static bool g16_for(int dt, int M, int bwd_tile) {
+  return dt == AAA_BF16 && fused_x(dt, M) && ab_int("AAA_GATES_F16", 1) && (tile_gates(BpttTiles{}, bwd_tile) & kG16);
+}
+static int bptt_tile(int dt, int M) { return step_tile(4L * cdiv(M, 32), "AAA_BPTT_TILE", true, dt == AAA_BF16); }
+bool gates_f16(int dt, int M) { return g16_for(dt, M, bptt_tile(dt, M)); }
+
+RecurPlan recur_plan(const Layout& L, bool resets) {
+  const int M = L.B * L.P;
+  RecurPlan p{};
+  p.fused_x = fused_x(L.dt, M);
+  p.bwd_tile = bptt_tile(L.dt, M);
+  p.fwd_tile = step_tile((long)(512 / 32) * cdiv(M, 32), "AAA_STEP_TILE", false, L.dt == AAA_BF16);
+  p.g16 = g16_for(L.dt, M, p.bwd_tile);
+  p.gate_bytes = p.g16 ? 2 : 4;
+  // The forward's path.  fp32: the frame-group launch, under a mask only where its RST variant exists (recur_f32.h
+  // f32_fwd_resets).  Then, with the fused x-part, bf16's band mode or frame-resident launch; else step by step.
+  const int G32 = f32_frames(L);
+  if (G32 && !(resets && !f32_fwd_resets(f32_split6(), G32, L.P))) p.fwd = RecurFwd::FramesF32, p.fwd_g = G32;
+  else if (!p.fused_x) p.fwd = RecurFwd::XpartSteps;
+  else if (const int nb = frames_band(L)) p.fwd = RecurFwd::BandBf16, p.fwd_g = nb;
+  else if (const int G = frames_g(L, "AAA_FRAMES_FWD")) p.fwd = RecurFwd::FramesBf16, p.fwd_g = G;
+  else p.fwd = RecurFwd::FusedSteps;
+  // The BPTT chain on the frame-resident kernels (recur_bwd.h; fp16 gate storage), only behind a frame-resident
+  // forward: band mode wherever the forward runs in band mode, else workgroups per frame as the forward's rule
+  // (AAA_FRAMES_BWD = 0 / 1 / 2 forces it).  The two share the channel-quad-major slices of Cst / Gt / dO
+  // (recur.h cqm4), which the per-step kernels do not read.
+  if (p.g16 && p.fwd == RecurFwd::BandBf16) p.fb = bw_band_fits(L.h, L.w) ? p.fwd_g : 0;
+  else if (p.g16 && p.fwd == RecurFwd::FramesBf16) p.fb = frames_g(L, "AAA_FRAMES_BWD");
+  // fp32: the frame-group BPTT behind the forward's G = 8 (a mask: its RST variant, the split-product kernel)
+  p.fb32 = L.dt == AAA_F32 && (!resets || f32_split6()) && G32 == 8 && env_int("AAA_F32_FRAMES_BWD", 1);
   static const int mask = ab_int("AAA_CQM", kCqmC | kCqmG | kCqmDO) & 7;   // A/B: tools/gpu_ab.sh
-  return frames_bwd(L, gates_f16(L.dt, L.B * L.P)) != 0 ? mask : 0;
+  p.cqm = p.fb ? mask : 0;
+  return p;
 }
 
 }  // namespace aaa

@@ -155,7 +155,7 @@ int vision_fwd(const Layout& L, int F, const char* pk, const float* prm, const v
   T* const rxp = xp_full && resident_xp ? Xp : nullptr;
   if constexpr (std::is_same<T, __bf16>::value && std::is_same<OT, __bf16>::value) {
     // bf16: the frame-resident encoder (vision.h), one launch; AAA_VIS_FRAMES=0 -> the layered kernels
-    if (vis_fits(L.H, L.W, L.H1, L.W1, L.h, L.w) && env_int("AAA_VIS_FRAMES", 1)) {
+    if (vis_frames_on(L)) {
       VisFwdParams vp{frames, (const __bf16*)(pk + L.k_Wp1), prm + L.poff[C0B], (const __bf16*)(pk + L.k_Wp2),
                       prm + L.poff[C1B], rxp, Y1, out, out_ld, F, L.H, L.W, L.H1, L.W1, L.h, L.w};
       HIPCHK(L.fu8 ? vision_fwd_frames<uint8_t>(vp, device_cus(), st) : vision_fwd_frames<float>(vp, device_cus(), st));
@@ -166,7 +166,7 @@ int vision_fwd(const Layout& L, int F, const char* pk, const float* prm, const v
   if constexpr (std::is_same<T, float>::value && std::is_same<OT, float>::value) {
     // fp32 split products: the frame-resident encoder (vision_f32.h), one launch, which also writes the
     // fp32 Y1 the backward reads; AAA_VIS_FRAMES=0 -> the layered kernels
-    if (f32_split6() && vis_fits(L.H, L.W, L.H1, L.W1, L.h, L.w) && env_int("AAA_VIS_FRAMES", 1)) {
+    if (f32_split6() && vis_frames_on(L)) {
       VisF32Params vp{frames, (const bf16x8*)(pk + L.k_W1s), prm + L.poff[C0B], (const bf16x8*)(pk + L.k_W2s),
                       prm + L.poff[C1B], rxp, Y1, out, out_ld, F, L.H, L.W, L.H1, L.W1, L.h, L.w};
       HIPCHK(L.fu8 ? vision_fwd_frames_f32<uint8_t>(vp, device_cus(), st)
@@ -189,163 +189,150 @@ int vision_fwd(const Layout& L, int F, const char* pk, const float* prm, const v
   return AAA_OK;
 }
 
+// ------------------------------------------------------------- forward ----
+// The phases of one forward call (forward_impl, at the end) share its CallCtx (rt.h).
+// conv1 + conv2 over all T*B frames -> XH[:, :, 0:64] of every slot
 template <typename T>
-static int forward_tail(const Layout& L, const aaa_io* io, hipStream_t st, const float* reset = nullptr);
+static int vision_forward(const CallCtx& c) {
+  const Layout& L = c.L;
+  TimerScope tim(AAA_TIMER_VISION_FWD, c.st, (double)L.F * vision_fwd_flop(L), "conv1 + conv2 (vision encoder)");
+  std::string ran;   // the kernels the dispatch took, for the timer's variant
+  const int rc = vision_fwd<T, T>(L, L.F, c.pk, c.prm, c.io->frames, c.Wt<T>(L.Xp), c.Wt<T>(L.Y1), c.Wt<T>(L.XH), 192,
+                                  c.st, L.xpc >= L.F, &ran, false);
+  if (rc) return rc;
+  tim.variant += ": " + ran;
+  return AAA_OK;
+}
 
+// initial state (reset(): zeros, attention.py:142-149) or carried state
 template <typename T>
-int forward_impl(const Layout& L, const aaa_io* io, hipStream_t st, int phases, const float* reset) {
-  // bf16 path: the fp32 tail GEMMs on the bf16 MFMA with split operands (AAA_TAIL_SPLIT3=0: fp32 MFMA)
-  TailPrecision tail_prec(std::is_same<T, __bf16>::value && env_int("AAA_TAIL_SPLIT3", 1),
-                          std::is_same<T, float>::value && f32_split6(), AAA_TIMER_TAIL_FWD);
-  char* ws = (char*)io->workspace;
-  const char* pk = (const char*)io->packed;
-  const float* prm = io->params;
-  auto Wf = [&](size_t off) { return (float*)(ws + off); };
-  auto Wt = [&](size_t off) { return (T*)(ws + off); };
-  const int F = L.F, M = L.B * L.P;
-  // fp32 h_t slices for the readout: fp32 path only (bf16 reads XH, readout_h)
-  auto hs_out = [&](int t) { return L.esz == 4 ? Wf(L.Hs) + (size_t)t * M * 128 : (float*)nullptr; };
-  // Episode starts (reset != null, fp32): before step t, zeros in the h half of XH slot t for the rows
-  // that enter it from reset() and a masked copy of c_{t-1} (in dC: the BPTT's carry, idle in the
-  // forward) -- Cst slot t keeps the true c_{t-1}, which step t-1's own backward reads (resets.hip).
-  // *cp <- the c_{t-1} the step's cell update reads.
-  auto c_in = [&](int t, const float** cp) -> int {
-    *cp = Wf(L.Cst) + (size_t)t * M * 128;
-    if (!reset) return AAA_OK;
-    HIPCHK(reset_rows(reset + (size_t)t * L.B, L.B, L.P,
-                      ResetZeros{}.add(Wf(L.XH) + (size_t)t * M * 192 + 64, 192, 128), *cp, Wf(L.dC), 128, st));
-    *cp = Wf(L.dC);
-    return AAA_OK;
-  };
+static int state_in(const CallCtx& c, bool core) {
+  const Layout& L = c.L;
+  const aaa_io* io = c.io;
+  const int M = L.B * L.P;
+  TimerScope tim(AAA_TIMER_MISC, c.st, 0.0, "state in/out copies, memsets, bias column sums");
+  // one launch: h_0 into XH slot 0, c_0 = 0 (reset) and the hand-off flags of this forward's
+  // multi-workgroup recurrence launch (zeroed here for every kernel choice)
+  ZeroRanges z{};
+  if (!io->c0) z.add(c.Wf(L.Cst), (long)M * 128);
+  if (core) z.add(c.Wf(L.rflags), (long)8 * L.B);
+  HIPCHK(prologue<T>(z, M, io->h0, c.Wt<T>(L.XH), 0, 0, 1, nullptr, nullptr, nullptr, c.st));
+  if (io->c0 && (c.plan.cqm & kCqmC)) HIPCHK(cqm_convert(io->c0, c.Wf(L.Cst), L.B, L.P, 1, c.st));
+  else if (io->c0) HIPCHK(hipMemcpyAsync(c.Wf(L.Cst), io->c0, (size_t)M * 128 * 4, hipMemcpyDeviceToDevice, c.st));
+  return AAA_OK;
+}
 
-  {  // conv1 + conv2 over all T*B frames -> XH[:, :, 0:64] of every slot
-    TimerScope tim(AAA_TIMER_VISION_FWD, st, (double)F * vision_fwd_flop(L), "conv1 + conv2 (vision encoder)");
-    std::string ran;   // the kernels the dispatch took, for the timer's variant
-    const int rc = vision_fwd<T, T>(L, F, pk, prm, io->frames, Wt(L.Xp), Wt(L.Y1), Wt(L.XH), 192, st, L.xpc >= F, &ran,
-                                    false);
+// fp32 h_t slice of step t for the readout: fp32 path only (bf16 reads XH, readout_h)
+static float* hs_out(const CallCtx& c, int t) {
+  return c.L.esz == 4 ? c.Wf(c.L.Hs) + (size_t)t * (c.L.B * c.L.P) * 128 : (float*)nullptr;
+}
+// Episode starts (reset != null, fp32): before step t, zeros in the h half of XH slot t for the rows
+// that enter it from reset() and a masked copy of c_{t-1} (in dC: the BPTT's carry, idle in the
+// forward) -- Cst slot t keeps the true c_{t-1}, which step t-1's own backward reads (resets.hip).
+// *cp <- the c_{t-1} the step's cell update reads.
+static int c_in(const CallCtx& c, int t, const float** cp) {
+  const Layout& L = c.L;
+  const int M = L.B * L.P;
+  *cp = c.Wf(L.Cst) + (size_t)t * M * 128;
+  if (!c.reset) return AAA_OK;
+  HIPCHK(reset_rows(c.reset + (size_t)t * L.B, L.B, L.P,
+                    ResetZeros{}.add(c.Wf(L.XH) + (size_t)t * M * 192 + 64, 192, 128), *cp, c.Wf(L.dC), 128, c.st));
+  *cp = c.Wf(L.dC);
+  return AAA_OK;
+}
+
+// fp32: one frame-group launch for all T steps, x-part included (recur_f32.h); under a mask its RST variant
+static int recur_frames_f32(const CallCtx& c) {
+  const Layout& L = c.L;
+  const aaa_io* io = c.io;
+  const int M = L.B * L.P, G = c.plan.fwd_g;
+  int* rep = nullptr;
+  if (const int rc = report_word("frame-group", &rep)) return rc;
+  RecF32Params rp{(const float*)(c.pk + L.k_Wf32), (const float*)(c.pk + L.k_bl), c.Wf(L.XH), c.Wf(L.Cst), c.Wf(L.Hs),
+                  c.Wf(L.Gt), (int*)(c.ws + L.rflags), rep, pair_budget(L.T), L.T, L.B, L.h, L.w, L.P, io->h0 ? 0 : 1, {}};
+  if (c.reset) {   // slot 0's h half of the rows that start an episode at step 0: the weight gradient's operand
+    rp.reset = c.reset;
+    if (io->h0)
+      HIPCHK(reset_rows(c.reset, L.B, L.P, ResetZeros{}.add(c.Wf(L.XH) + 64, 192, 128), nullptr, nullptr, 0, c.st));
+  }
+  const bool s6 = f32_split6();
+  rp.Wf6 = (const u32x2*)(c.pk + L.k_Wf6);
+  rp.Wf6p = (const u32x4*)(c.pk + L.k_Wf6p);
+  TimerScope tim(AAA_TIMER_FWD_STEP, c.st, 2.0 * M * 512 * (576.0 * L.T + 1152.0 * (L.T - (io->h0 ? 0 : 1))),
+                 strf("fp32 frame-group [x|h] recurrence%s, %d steps per launch, %d WG per frame [kernel: %s]%s",
+                      s6 ? " (bf16x6 split products)" : "", L.T, G,
+                      f32_fwd_presplit(s6, G, L.P) ? "k_convlstm_fwd_f32ps" : "k_convlstm_fwd_f32<", c.reset ? ", resets" : ""));
+  HIPCHK(convlstm_fwd_f32(rp, G, c.st, s6));
+  return AAA_OK;
+}
+
+// bf16: one frame-resident launch for all T steps (recur.h) -- band mode (fwd_g bands per frame), or one
+// workgroup or a pair per frame.  GT: the gate storage type.
+template <typename GT>
+static int recur_frames_bf16(const CallCtx& c) {
+  const Layout& L = c.L;
+  const bool band = c.plan.fwd == RecurFwd::BandBf16;
+  const int M = L.B * L.P, G = c.plan.fwd_g;
+  int* rep = nullptr;
+  if (band || G == 2)   // hand-off between a frame's workgroups
+    if (const int rc = report_word(band ? "band-mode" : "paired-kernel", &rep)) return rc;
+  RecFwdParams<GT> rp{(const __bf16*)(c.pk + L.k_Wfr), (const float*)(c.pk + L.k_bl), c.Wt<__bf16>(L.XH), c.Wf(L.Cst),
+                      nullptr, (GT*)(c.ws + L.Gt), (int*)(c.ws + L.rflags), L.T, L.B, L.h, L.w, L.P, rep,
+                      pair_budget(L.T), rec_stagger("AAA_REC_STAGGER_FWD")};
+  rp.cqm = c.plan.cqm;
+  // row-padded h image (recur.h rec_rowpad): measured neutral to 1 % slower (C3 forward 1234-1242 vs
+  // 1247-1269 us, profiles/r06/ab/rowpad_fwd/), so an A/B option (AAA_REC_ROWPAD=1, ablation builds)
+  if (!band) rp.rowpad = ab_int("AAA_REC_ROWPAD", 0) ? rec_rowpad(L.h, L.w) : 0;
+  TimerScope tim(AAA_TIMER_FWD_STEP, c.st, 2.0 * M * 512 * 1728 * L.T,
+                 band ? strf("bf16 band-mode frame-resident [x|h] recurrence, %d steps per launch, %d bands per frame "
+                             "[kernel: k_convlstm_fwd_frames+Lb1E]", L.T, G)
+                      : strf("bf16 frame-resident [x|h] recurrence, %d steps per launch, %d WG per frame%s [kernel: k_convlstm_fwd_frames+Lb0E]",
+                             L.T, G, rp.rowpad ? ", row-padded h image" : ""));
+  HIPCHK(band ? convlstm_fwd_frames_band<GT>(rp, c.st) : convlstm_fwd_frames<GT>(rp, G, c.st));
+  return AAA_OK;
+}
+
+// Per step, the x-part riding in the step's GEMM (K over the whole XH slot, [x_t | h_{t-1}], bias in the
+// epilogue): no batched x-part GEMM and no fp32 x-part round trip through HBM (tools/ubench/bf16_tiles: the
+// step's epilogue traffic, not its MFMAs, is half its time).  The tiles and their measurements: rt.h fused_step.
+template <typename T, typename GT>
+static int recur_fused_steps(const CallCtx& c) {
+  const Layout& L = c.L;
+  const int M = L.B * L.P;
+  for (int t = 0; t < L.T; ++t) {   // ConvLSTM (attention.py:110-126), x- and h-part together
+    const float* cp;
+    if (const int rc = c_in(c, t, &cp)) return rc;
+    EpiConvLstmFwd<T, GT> ep{cp, c.Wf(L.Cst) + (size_t)(t + 1) * M * 128, hs_out(c, t),
+                             c.Wt<T>(L.XH) + (size_t)(t + 1) * M * 192, (GT*)(c.ws + L.Gt) + (size_t)t * M * 512, M,
+                             (const float*)(c.pk + L.k_bl)};
+    const int rc = fused_step<T, GT>((const T*)(c.pk + L.k_WpXH), c.Wt<T>(L.XH) + (size_t)t * M * 192, L.h, L.w, M, ep,
+                                     c.st, L.dhs ? c.Wf(L.dhs) : nullptr, c.reset != nullptr);
     if (rc) return rc;
-    tim.variant += ": " + ran;
   }
-  {  // initial state (reset(): zeros, attention.py:142-149) or carried state
-    TimerScope tim(AAA_TIMER_MISC, st, 0.0, "state in/out copies, memsets, bias column sums");
-    // one launch: h_0 into XH slot 0, c_0 = 0 (reset) and the hand-off flags of this forward's
-    // multi-workgroup recurrence launch (zeroed here for every kernel choice)
-    ZeroRanges z{};
-    if (!io->c0) z.add(Wf(L.Cst), (long)M * 128);
-    if (phases & AAA_FWD_CORE) z.add(Wf(L.rflags), (long)8 * L.B);
-    HIPCHK(prologue<T>(z, M, io->h0, Wt(L.XH), 0, 0, 1, nullptr, nullptr, nullptr, st));
-    if (io->c0 && (cqm_layout(L) & kCqmC)) HIPCHK(cqm_convert(io->c0, Wf(L.Cst), L.B, L.P, 1, st));
-    else if (io->c0) HIPCHK(hipMemcpyAsync(Wf(L.Cst), io->c0, (size_t)M * 128 * 4, hipMemcpyDeviceToDevice, st));
-  }
-  // no CORE (aaa_forward_phases, fp32): the recurrence's products are already in
-  // Gt / Cst / Hs / XH (aaa_core_import)
-  if (!(phases & AAA_FWD_CORE)) return forward_tail<T>(L, io, st, reset);
-  // the h-part tile of the per-step chain below (looked up here: an unknown id is refused whichever kernel runs)
-  const int fwd_tile = step_tile((long)(512 / 32) * cdiv(M, 32), "AAA_STEP_TILE", false, L.dt == AAA_BF16);
-  if (fwd_tile < 0) return tile_unknown("AAA_STEP_TILE");
-  if constexpr (std::is_same<T, float>::value) {
-    // (a mask: the frame-group kernels' RST variants where they exist, recur_f32.h f32_fwd_resets, else the
-    // per-step kernels below)
-    int Gf = f32_frames(L);
-    if (reset && Gf && !f32_fwd_resets(f32_split6(), Gf, L.P)) Gf = 0;
-    if (const int G = Gf) {   // one frame-group launch for all T steps, x-part included (recur_f32.h)
-      int* rep = nullptr;
-      if (const int rc = report_word("frame-group", &rep)) return rc;
-      RecF32Params rp{(const float*)(pk + L.k_Wf32), (const float*)(pk + L.k_bl), Wf(L.XH), Wf(L.Cst), Wf(L.Hs),
-                      Wf(L.Gt), (int*)(ws + L.rflags), rep, pair_budget(L.T), L.T, L.B, L.h, L.w, L.P,
-                      io->h0 ? 0 : 1, {}};
-      if (reset) {   // slot 0's h half of the rows that start an episode at step 0: the weight gradient's operand
-        rp.reset = reset;
-        if (io->h0)
-          HIPCHK(reset_rows(reset, L.B, L.P, ResetZeros{}.add(Wf(L.XH) + 64, 192, 128), nullptr, nullptr, 0, st));
-      }
-      {
-        const bool s6 = f32_split6();
-        rp.Wf6 = (const u32x2*)(pk + L.k_Wf6);
-        rp.Wf6p = (const u32x4*)(pk + L.k_Wf6p);
-        TimerScope tim(AAA_TIMER_FWD_STEP, st, 2.0 * M * 512 * (576.0 * L.T + 1152.0 * (L.T - (io->h0 ? 0 : 1))),
-                       strf("fp32 frame-group [x|h] recurrence%s, %d steps per launch, %d WG per frame [kernel: %s]%s",
-                            s6 ? " (bf16x6 split products)" : "", L.T, G,
-                            f32_fwd_presplit(s6, G, L.P) ? "k_convlstm_fwd_f32ps" : "k_convlstm_fwd_f32<",
-                            reset ? ", resets" : ""));
-        HIPCHK(convlstm_fwd_f32(rp, G, st, s6));
-      }
-      return forward_tail<T>(L, io, st, reset);
-    }
-  }
-  // bf16: the x-part rides in each step's GEMM (K over the whole XH slot,
-  // [x_t | h_{t-1}], bias in the epilogue): no batched x-part GEMM and no
-  // fp32 x-part round trip through HBM (tools/ubench/bf16_tiles: the step's
-  // epilogue traffic, not its MFMAs, is half its time).  AAA_FUSED_X=0/1 overrides.
-  if (fused_x(L.dt, M)) {
-    const T* WpXH = (const T*)(pk + L.k_WpXH);
-    // bf16: 128x128 tiles of 4 waves (64x64 per wave: twice the MFMA work per
-    // fragment read of the 128x64 8-wave tile) -- C3 94.7 -> 81-83 us, C4 51.5 ->
-    // 44.6 us, C5 90.7 -> 78.6-79.5 us per step (tools/ab_fused.sh); fp32 (only
-    // small M, e.g. the B=1 actor, fuses the x-part): 128x64 8 waves.
-    auto steps = [&](auto gtag) -> int {
-      using GT = decltype(gtag);
-      if constexpr (!std::is_same<T, float>::value) {
-        if (const int NBd = frames_band(L)) {   // one band-mode launch for all T steps (recur.h BAND)
-          int* rep = nullptr;
-          if (const int rc = report_word("band-mode", &rep)) return rc;
-          RecFwdParams<GT> rp{(const __bf16*)(pk + L.k_Wfr), (const float*)(pk + L.k_bl), Wt(L.XH), Wf(L.Cst),
-                              nullptr, (GT*)(ws + L.Gt), (int*)(ws + L.rflags), L.T, L.B, L.h, L.w, L.P,
-                              rep, pair_budget(L.T), rec_stagger("AAA_REC_STAGGER_FWD")};
-          rp.cqm = cqm_layout(L);
-          TimerScope tim(AAA_TIMER_FWD_STEP, st, 2.0 * M * 512 * 1728 * L.T,
-                         strf("bf16 band-mode frame-resident [x|h] recurrence, %d steps per launch, %d bands per frame "
-                              "[kernel: k_convlstm_fwd_frames+Lb1E]", L.T, NBd));
-          HIPCHK(convlstm_fwd_frames_band<GT>(rp, st));
-          return AAA_OK;
-        }
-        if (const int G = frames_fwd(L)) {   // one frame-resident launch for all T steps (recur.h)
-          int* rep = nullptr;
-          if (G == 2)
-            if (const int rc = report_word("paired-kernel", &rep)) return rc;
-          RecFwdParams<GT> rp{(const __bf16*)(pk + L.k_Wfr), (const float*)(pk + L.k_bl), Wt(L.XH), Wf(L.Cst),
-                              nullptr, (GT*)(ws + L.Gt), (int*)(ws + L.rflags), L.T, L.B, L.h, L.w, L.P,
-                              rep, pair_budget(L.T), rec_stagger("AAA_REC_STAGGER_FWD")};
-          rp.cqm = cqm_layout(L);
-          // row-padded h image (recur.h rec_rowpad): measured neutral to 1 % slower (C3 forward 1234-1242 vs
-          // 1247-1269 us, profiles/r06/ab/rowpad_fwd/), so an A/B option (AAA_REC_ROWPAD=1, ablation builds)
-          rp.rowpad = ab_int("AAA_REC_ROWPAD", 0) ? rec_rowpad(L.h, L.w) : 0;
-          TimerScope tim(AAA_TIMER_FWD_STEP, st, 2.0 * M * 512 * 1728 * L.T,
-                         strf("bf16 frame-resident [x|h] recurrence, %d steps per launch, %d WG per frame%s [kernel: k_convlstm_fwd_frames+Lb0E]",
-                              L.T, G, rp.rowpad ? ", row-padded h image" : ""));
-          HIPCHK(convlstm_fwd_frames<GT>(rp, G, st));
-          return AAA_OK;
-        }
-      }
-      for (int t = 0; t < L.T; ++t) {   // ConvLSTM (attention.py:110-126), x- and h-part together
-        const float* cp;
-        if (const int rc = c_in(t, &cp)) return rc;
-        EpiConvLstmFwd<T, GT> ep{cp, Wf(L.Cst) + (size_t)(t + 1) * M * 128,
-                                 hs_out(t), Wt(L.XH) + (size_t)(t + 1) * M * 192,
-                                 (GT*)(ws + L.Gt) + (size_t)t * M * 512, M, (const float*)(pk + L.k_bl)};
-        const int rc = fused_step<T, GT>(WpXH, Wt(L.XH) + (size_t)t * M * 192, L.h, L.w, M, ep, st,
-                                         L.dhs ? Wf(L.dhs) : nullptr, reset != nullptr);
-        if (rc) return rc;
-      }
-      return AAA_OK;
-    };
-    const int rc = gates_f16(L.dt, M) ? steps(_Float16{}) : steps(float{});
-    if (rc) return rc;
-    return forward_tail<T>(L, io, st, reset);
-  }
-  // x-part of the ConvLSTM steps (not recurrent): Gt <- Wx * x_t + b, in
-  // chunks of ``cs`` steps on the aux stream; step t waits only for its chunk.
+  return AAA_OK;
+}
+
+// The x-part of the ConvLSTM steps (not recurrent), batched: Gt <- Wx * x_t + b, in chunks of ``cs`` steps on
+// the aux stream; then the h-part step by step, step t waiting only for its chunk.
+template <typename T>
+static int recur_xpart_steps(const CallCtx& c) {
+  const Layout& L = c.L;
+  const hipStream_t st = c.st;
+  const int M = L.B * L.P, fwd_tile = c.plan.fwd_tile;
   hipStream_t ax = aux_stream();
   const int cs = chunk_steps(L);
   hipStream_t xs = ax ? ax : st;
   if (ax) HIPCHK(stream_order(st, ax));
-  auto xpart = [&](int lo, int hi) -> int {
+  hipEvent_t xev[64];
+  const int nchunks = (L.T + cs - 1) / cs;
+  if (ax && nchunks > 48) return fail(AAA_E_ARG, "too many overlap chunks (T=%d, AAA_CHUNK=%d)", L.T, cs);
+  for (int k = 0; k < nchunks; ++k) {   // the x-part of steps [lo, hi)
+    const int lo = k * cs, hi = std::min(L.T, (k + 1) * cs), rows = (hi - lo) * M;
     // 64x64 tiles (128x128 measured slower: K is only 576)
     const ConvGeo g = ConvGeo{64, 192, 0, L.h, L.w, L.h, L.w, 3, 1, 1, 0}.prep();
-    const int rows = (hi - lo) * M;
-    EpiStoreT<float> ep{Wf(L.Gt) + (size_t)lo * M * 512, 512, 512, rows, (const float*)(pk + L.k_bl), 0};
-    const T* WpX = (const T*)(pk + L.k_WpX);
-    const T* xs0 = Wt(L.XH) + (size_t)lo * M * 192;
+    EpiStoreT<float> ep{c.Wf(L.Gt) + (size_t)lo * M * 512, 512, 512, rows, (const float*)(c.pk + L.k_bl), 0};
+    const T* WpX = (const T*)(c.pk + L.k_WpX);
+    const T* xs0 = c.Wt<T>(L.XH) + (size_t)lo * M * 192;
     const uint32_t xb = (uint32_t)((size_t)(hi - lo) * M * 192 * L.esz);
     switch (pipe_batched() ? ab_int("AAA_XPART_TILE", 0) : -1) {   // A/B: tools/ab_batched.sh
       case -1: HIPCHK((step_gemm<CfgFor<T>, false>(WpX, 576, 512, xs0, g, rows, xb, ep, 512, 576, xs))); break;
@@ -361,33 +348,24 @@ int forward_impl(const Layout& L, const aaa_io* io, hipStream_t st, int phases, 
 #endif
       default: HIPCHK((step_gemm<CfgFor<T>, true>(WpX, 576, 512, xs0, g, rows, xb, ep, 512, 576, xs))); break;
     }
-    return AAA_OK;
-  };
-  hipEvent_t xev[64];
-  const int nchunks = (L.T + cs - 1) / cs;
-  if (ax && nchunks > 48) return fail(AAA_E_ARG, "too many overlap chunks (T=%d, AAA_CHUNK=%d)", L.T, cs);
-  for (int k = 0; k < nchunks; ++k) {
-    int rc = xpart(k * cs, std::min(L.T, (k + 1) * cs));
-    if (rc) return rc;
     if (ax) HIPCHK(record_event(ax, &xev[k]));
   }
   const uint32_t xh_bytes = (uint32_t)((size_t)M * 192 * L.esz);  // one step slice of XH
   for (int t = 0; t < L.T; ++t) {  // ConvLSTM recurrence (attention.py:110-126): h-part only
     if (ax && t % cs == 0) HIPCHK(hipStreamWaitEvent(st, xev[t / cs], 0));   // x-part of steps [t, t+cs) done
     const float* cp;
-    if (const int rc = c_in(t, &cp)) return rc;
-    if (t == 0 && !io->h0) {       // zero state: gates come from the x-part alone
-      HIPCHK(gate_fwd_zx<T>(M, cp, Wf(L.Gt), Wf(L.Cst) + (size_t)M * 128, hs_out(0), Wt(L.XH) + (size_t)M * 192,
-                            st));
+    if (const int rc = c_in(c, t, &cp)) return rc;
+    if (t == 0 && !c.io->h0) {       // zero state: gates come from the x-part alone
+      HIPCHK(gate_fwd_zx<T>(M, cp, c.Wf(L.Gt), c.Wf(L.Cst) + (size_t)M * 128, hs_out(c, 0),
+                            c.Wt<T>(L.XH) + (size_t)M * 192, st));
       continue;
     }
-    EpiConvLstmFwd<T> ep{cp, Wf(L.Cst) + (size_t)(t + 1) * M * 128,
-                         hs_out(t), Wt(L.XH) + (size_t)(t + 1) * M * 192,
-                         Wf(L.Gt) + (size_t)t * M * 512, M};
+    EpiConvLstmFwd<T> ep{cp, c.Wf(L.Cst) + (size_t)(t + 1) * M * 128, hs_out(c, t),
+                         c.Wt<T>(L.XH) + (size_t)(t + 1) * M * 192, c.Wf(L.Gt) + (size_t)t * M * 512, M};
     const ConvGeo g = ConvGeo{128, 192, 64, L.h, L.w, L.h, L.w, 3, 1, 1, 0}.prep();
-    TimerScope tim(AAA_TIMER_FWD_STEP, st, 2.0 * M * 512 * 1152, strf("%s h-part step (x-part batched), K=1152, tile %d [kernel: EpiConvLstmFwd]%s", std::is_same<T, float>::value ? "fp32" : "bf16", fwd_tile, reset ? ", resets" : ""));
-    const T* WpH = (const T*)(pk + L.k_WpH);
-    const T* xh = Wt(L.XH) + (size_t)t * M * 192;
+    TimerScope tim(AAA_TIMER_FWD_STEP, st, 2.0 * M * 512 * 1152, strf("%s h-part step (x-part batched), K=1152, tile %d [kernel: EpiConvLstmFwd]%s", std::is_same<T, float>::value ? "fp32" : "bf16", fwd_tile, c.reset ? ", resets" : ""));
+    const T* WpH = (const T*)(c.pk + L.k_WpH);
+    const T* xh = c.Wt<T>(L.XH) + (size_t)t * M * 192;
     const hipError_t e = for_tile<FwdTiles>(fwd_tile, hipErrorInvalidValue, [&](auto tile) {
       using Tl = decltype(tile);
       return step_gemm<typename Tl::template Cfg<T>, Tl::stage != Stage::Reg, T, T, EpiConvLstmFwd<T>, Tl::NBUF, Tl::ILV>(
@@ -395,7 +373,34 @@ int forward_impl(const Layout& L, const aaa_io* io, hipStream_t st, int phases, 
     });
     HIPCHK(e);
   }
-  return forward_tail<T>(L, io, st, reset);
+  return AAA_OK;
+}
+
+// The ConvLSTM recurrence on the plan's path, with fp16 or fp32 gate storage
+template <typename T>
+static int core_forward(const CallCtx& c) {
+  const RecurPlan& p = c.plan;
+  // (the h-part tile of the per-step chain: an unknown id is refused whichever kernel runs)
+  if (p.fwd_tile < 0) return tile_unknown("AAA_STEP_TILE");
+  if constexpr (std::is_same<T, float>::value) {
+    if (p.fwd == RecurFwd::FramesF32) return recur_frames_f32(c);
+  } else if (p.fwd == RecurFwd::BandBf16 || p.fwd == RecurFwd::FramesBf16) {
+    return p.g16 ? recur_frames_bf16<_Float16>(c) : recur_frames_bf16<float>(c);
+  }
+  if (p.fwd == RecurFwd::XpartSteps) return recur_xpart_steps<T>(c);
+  return p.g16 ? recur_fused_steps<T, _Float16>(c) : recur_fused_steps<T, float>(c);
+}
+
+// answer_processor.0 + ReLU and answer_processor.2 (attention.py:277-282, 350) over ``rows`` frames from f0:
+// their answer rows -> hid1 -> ``out`` (pitch out_ld)
+static int answer_mlp(const CallCtx& c, size_t f0, int rows, float* out, int out_ld) {
+  const Layout& L = c.L;
+  float* hid = c.Wf(L.hid1) + f0 * 512;
+  HIPCHK(tail_gemm({(const float*)(c.pk + L.k_W1p), L.ans_ld, 512}, {c.Wf(L.ans) + f0 * L.ans_ld, L.ans_ld, rows},
+                   EpiStoreT<float>{hid, 512, 512, rows, c.prm + L.poff[A0B], 1}, 512, rows, L.ans_ld, c.st));
+  HIPCHK(tail_gemm({c.prm + L.poff[A2W], 512, 256}, {hid, 512, rows},
+                   EpiStoreT<float>{out, out_ld, 256, rows, c.prm + L.poff[A2B], 0}, 256, rows, 512, c.st));
+  return AAA_OK;
 }
 
 // Stateful policy core (AAA_FLAG_STATEFUL_CORE; the reference's else branch,
@@ -406,14 +411,14 @@ int forward_impl(const Layout& L, const aaa_io* io, hipStream_t st, int phases, 
 // zeros); the LSTMCell epilogue also writes h_t into step t+1's [answer | h]
 // GEMM row, so each step is five small GEMMs and one attention launch.  The
 // heads then run batched over all frames on CH[1..T].
-static int forward_tail_stateful(const Layout& L, const aaa_io* io, hipStream_t st, const float* reset) {
-  char* ws = (char*)io->workspace;
-  const char* pk = (const char*)io->packed;
-  const float* prm = io->params;
-  auto Wf = [&](size_t off) { return (float*)(ws + off); };
+static int forward_tail_stateful(const CallCtx& c) {
+  const Layout& L = c.L;
+  const aaa_io* io = c.io;
+  const hipStream_t st = c.st;
+  const float* prm = c.prm;
   const int B = L.B, P = L.P, qd = L.qd;
   const size_t sB = (size_t)B * 256 * 4;
-  float *CH = Wf(L.CH), *CC = Wf(L.CC), *AOX = Wf(L.AOX);
+  float *CH = c.Wf(L.CH), *CC = c.Wf(L.CC), *AOX = c.Wf(L.AOX);
   if (io->core_h0) HIPCHK(hipMemcpyAsync(CH, io->core_h0, sB, hipMemcpyDeviceToDevice, st));
   else HIPCHK(hipMemsetAsync(CH, 0, sB, st));
   if (io->core_c0) HIPCHK(hipMemcpyAsync(CC, io->core_c0, sB, hipMemcpyDeviceToDevice, st));
@@ -421,9 +426,9 @@ static int forward_tail_stateful(const Layout& L, const aaa_io* io, hipStream_t 
   HIPCHK(hipMemcpy2DAsync(AOX + 256, 512 * 4, CH, 256 * 4, 256 * 4, B, hipMemcpyDeviceToDevice, st));
   for (int t = 0; t < L.T; ++t) {
     const size_t f0 = (size_t)t * B;
-    float* q1 = Wf(L.q1s) + f0 * 128;
-    float* q2 = Wf(L.q2s) + f0 * qd;
-    float* Qt = Wf(L.Qf) + f0 * qd;
+    float* q1 = c.Wf(L.q1s) + f0 * 128;
+    float* q2 = c.Wf(L.q2s) + f0 * qd;
+    float* Qt = c.Wf(L.Qf) + f0 * qd;
     // Episode starts: zeros in the h half of this step's [answer | h] rows for the rows that enter it
     // from reset(), and a masked copy of c_{t-1} (in dcc: the backward's carry, idle here); the query
     // MLP then reads h_{t-1} from those rows, its second copy.  CH / CC slot t keep the true
@@ -431,11 +436,11 @@ static int forward_tail_stateful(const Layout& L, const aaa_io* io, hipStream_t 
     const float* hq = CH + f0 * 256;
     const float* cprev = CC + f0 * 256;
     int hq_ld = 256;
-    if (reset) {
-      HIPCHK(reset_rows(reset + f0, B, 1, ResetZeros{}.add(AOX + f0 * 512 + 256, 512, 256), cprev, Wf(L.dcc), 256, st));
+    if (c.reset) {
+      HIPCHK(reset_rows(c.reset + f0, B, 1, ResetZeros{}.add(AOX + f0 * 512 + 256, 512, 256), cprev, c.Wf(L.dcc), 256, st));
       hq = AOX + f0 * 512 + 256;
       hq_ld = 512;
-      cprev = Wf(L.dcc);
+      cprev = c.Wf(L.dcc);
     }
     // QueryNetwork(prev_output = h_{t-1}) (attention.py:184-198, 331)
     HIPCHK(tail_gemm({prm + L.poff[Q0W], 256, 128}, {hq, hq_ld, B},
@@ -447,82 +452,87 @@ static int forward_tail_stateful(const Layout& L, const aaa_io* io, hipStream_t 
     // attention readout with this step's per-frame queries (basis logits in-kernel)
     {
       TimerScope tim(AAA_TIMER_ATTN_FWD, st, (double)B * attn_fwd_bytes(P, L.nq, L.ans_ld, L.esz), L.esz == 2 ? "k_attn_fwd_mfma, per-frame query (stateful core)" : "k_attn_fwd, per-frame query (stateful core)");
-      HIPCHK(attn_fwd(readout_h(L, ws).frame(f0, P), io->basis, Qt, nullptr, io->prev_reward ? io->prev_reward + f0 : nullptr,
-                      io->prev_action ? io->prev_action + f0 : nullptr, B, P, L.nq, Wf(L.Am) + f0 * P * L.nq,
-                      Wf(L.ans) + f0 * L.ans_ld, L.ans_ld, st, qd));
+      HIPCHK(attn_fwd(readout_h(L, c.ws).frame(f0, P), io->basis, Qt, nullptr, io->prev_reward ? io->prev_reward + f0 : nullptr,
+                      io->prev_action ? io->prev_action + f0 : nullptr, B, P, L.nq, c.Wf(L.Am) + f0 * P * L.nq,
+                      c.Wf(L.ans) + f0 * L.ans_ld, L.ans_ld, st, qd));
     }
-    // answer_processor.0 + ReLU
-    HIPCHK(tail_gemm({(const float*)(pk + L.k_W1p), L.ans_ld, 512}, {Wf(L.ans) + f0 * L.ans_ld, L.ans_ld, B},
-                     EpiStoreT<float>{Wf(L.hid1) + f0 * 512, 512, 512, B, prm + L.poff[A0B], 1}, 512, B, L.ans_ld, st));
-    // answer_processor.2 -> the answer half of this step's [answer | h_{t-1}] rows
-    HIPCHK(tail_gemm({prm + L.poff[A2W], 512, 256}, {Wf(L.hid1) + f0 * 512, 512, B},
-                     EpiStoreT<float>{AOX + f0 * 512, 512, 256, B, prm + L.poff[A2B], 0}, 256, B, 512, st));
+    // the answer MLP -> the answer half of this step's [answer | h_{t-1}] rows
+    if (const int rc = answer_mlp(c, f0, B, AOX + f0 * 512, 512)) return rc;
     // policy_core LSTMCell from (h_{t-1}, c_{t-1}) (attention.py:356-358)
-    HIPCHK(tail_gemm({(const float*)(pk + L.k_Wihhp), 512, 1024}, {AOX + f0 * 512, 512, B},
-                     EpiLstmCellFwdS{(const float*)(pk + L.k_blc), Wf(L.LG) + f0 * 1024, cprev, CC + (f0 + B) * 256,
+    HIPCHK(tail_gemm({(const float*)(c.pk + L.k_Wihhp), 512, 1024}, {AOX + f0 * 512, 512, B},
+                     EpiLstmCellFwdS{(const float*)(c.pk + L.k_blc), c.Wf(L.LG) + f0 * 1024, cprev, CC + (f0 + B) * 256,
                                      CH + (f0 + B) * 256, t + 1 < L.T ? AOX + (f0 + B) * 512 + 256 : nullptr, B},
                      1024, B, 512, st));
   }
   if (io->attn)
-    HIPCHK(hipMemcpyAsync(io->attn, Wf(L.Am), (size_t)L.F * P * L.nq * 4, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(io->attn, c.Wf(L.Am), (size_t)L.F * P * L.nq * 4, hipMemcpyDeviceToDevice, st));
   return AAA_OK;
 }
 
-// Everything after the ConvLSTM: query, attention readout, answer MLP,
-// LSTMCell, heads (all batched over the T*B frames, Q1) and state outputs.
-template <typename T>
-static int forward_tail(const Layout& L, const aaa_io* io, hipStream_t st, const float* reset) {
-  char* ws = (char*)io->workspace;
-  const char* pk = (const char*)io->packed;
-  const float* prm = io->params;
-  auto Wf = [&](size_t off) { return (float*)(ws + off); };
-  const int F = L.F, P = L.P, M = L.B * L.P;
-  if (L.sc) {   // stateful core: the tail runs step by step
-    const int rc = forward_tail_stateful(L, io, st, reset);
-    if (rc) return rc;
-  } else {
+// The zero-state tail (Q1): the constant query, the attention readout, the answer MLP and the LSTMCell, all
+// batched over the T*B frames
+static int forward_tail_batched(const CallCtx& c) {
+  const Layout& L = c.L;
+  const aaa_io* io = c.io;
+  const hipStream_t st = c.st;
+  const int F = L.F, P = L.P;
   // constant query (Q1) + fused attention readout over all T*B frames
-  const float* Qc = (const float*)(pk + L.k_Q);
+  const float* Qc = (const float*)(c.pk + L.k_Q);
   {
     TimerScope tim(AAA_TIMER_TAIL_FWD, st, 0.0, "query basis logits");
-    HIPCHK(query_sq(io->basis, Qc, P, L.nq, Wf(L.SQ), st));
+    HIPCHK(query_sq(io->basis, Qc, P, L.nq, c.Wf(L.SQ), st));
   }
   {
     TimerScope tim(AAA_TIMER_ATTN_FWD, st, (double)F * attn_fwd_bytes(P, L.nq, L.ans_ld, L.esz), L.esz == 2 ? "k_attn_fwd_mfma (readout on the MFMA, map and basis in bf16 parts), 1 WG per frame" : "k_attn_fwd (VALU), 1 WG per frame");
-    HIPCHK(attn_fwd(readout_h(L, ws), io->basis, Qc, Wf(L.SQ), io->prev_reward, io->prev_action, F, P, L.nq, Wf(L.Am),
-                    Wf(L.ans), L.ans_ld, st));
+    HIPCHK(attn_fwd(readout_h(L, c.ws), io->basis, Qc, c.Wf(L.SQ), io->prev_reward, io->prev_action, F, P, L.nq,
+                    c.Wf(L.Am), c.Wf(L.ans), L.ans_ld, st));
   }
   TimerScope tim(AAA_TIMER_TAIL_FWD, st, (double)F * tail_fwd_flop(L), "answer MLP + LSTMCell + heads (fp32 GEMMs)");
-  if (io->attn) HIPCHK(hipMemcpyAsync(io->attn, Wf(L.Am), (size_t)F * P * L.nq * 4, hipMemcpyDeviceToDevice, st));
-  // answer_processor.0 + ReLU (attention.py:277-282, 350)
-  HIPCHK(tail_gemm({(const float*)(pk + L.k_W1p), L.ans_ld, 512}, {Wf(L.ans), L.ans_ld, F},
-                   EpiStoreT<float>{Wf(L.hid1), 512, 512, F, prm + L.poff[A0B], 1}, 512, F, L.ans_ld, st));
-  // answer_processor.2
-  HIPCHK(tail_gemm({prm + L.poff[A2W], 512, 256}, {Wf(L.hid1), 512, F},
-                   EpiStoreT<float>{Wf(L.AO), 256, 256, F, prm + L.poff[A2B], 0}, 256, F, 512, st));
+  if (io->attn) HIPCHK(hipMemcpyAsync(io->attn, c.Wf(L.Am), (size_t)F * P * L.nq * 4, hipMemcpyDeviceToDevice, st));
+  if (const int rc = answer_mlp(c, 0, F, c.Wf(L.AO), 256)) return rc;
   // policy_core LSTMCell from zero state (attention.py:354-355)
-  HIPCHK(tail_gemm({(const float*)(pk + L.k_Wihp), 256, 1024}, {Wf(L.AO), 256, F},
-                   EpiLstmCellFwd{(const float*)(pk + L.k_blc), Wf(L.LG), Wf(L.LC), Wf(L.LH), F}, 1024, F, 256, st));
-  }
+  HIPCHK(tail_gemm({(const float*)(c.pk + L.k_Wihp), 256, 1024}, {c.Wf(L.AO), 256, F},
+                   EpiLstmCellFwd{(const float*)(c.pk + L.k_blc), c.Wf(L.LG), c.Wf(L.LC), c.Wf(L.LH), F}, 1024, F, 256, st));
+  return AAA_OK;
+}
+
+// Everything after the ConvLSTM: query, attention readout, answer MLP, LSTMCell (batched over the T*B frames,
+// or step by step for the stateful core), then the heads over all frames and the state outputs.
+static int forward_tail(const CallCtx& c) {
+  const Layout& L = c.L;
+  const aaa_io* io = c.io;
+  const hipStream_t st = c.st;
+  const int F = L.F, M = L.B * L.P;
+  const size_t sB = (size_t)L.B * 256;   // one slot of the stateful core's CH / CC
+  if (const int rc = L.sc ? forward_tail_stateful(c) : forward_tail_batched(c)) return rc;
   TimerScope tim(AAA_TIMER_TAIL_FWD, st, L.sc ? 0.0 : 2.0 * F * 256 * 2 * L.A, "policy/value heads + state out");
   // policy / values heads (attention.py:365-367), batched over all frames
-  HIPCHK(tail_gemm({(const float*)(pk + L.k_Whd), 256, 2 * L.A}, {L.sc ? Wf(L.CH) + (size_t)L.B * 256 : Wf(L.LH), 256, F},
-                   EpiHeads{io->logits, io->values, (const float*)(pk + L.k_bhd), L.A, F}, 2 * L.A, F, 256, st));
+  HIPCHK(tail_gemm({(const float*)(c.pk + L.k_Whd), 256, 2 * L.A},
+                   {L.sc ? c.Wf(L.CH) + sB : c.Wf(L.LH), 256, F},
+                   EpiHeads{io->logits, io->values, (const float*)(c.pk + L.k_bhd), L.A, F}, 2 * L.A, F, 256, st));
   if (io->hT && L.esz == 2)   // h_{T-1} from XH slot T (the bf16 path keeps no fp32 h_t)
-    HIPCHK(xh_to_state<__bf16>(M, (const __bf16*)(ws + L.XH) + (size_t)L.T * M * 192, io->hT, st));
+    HIPCHK(xh_to_state<__bf16>(M, (const __bf16*)(c.ws + L.XH) + (size_t)L.T * M * 192, io->hT, st));
   else if (io->hT)
-    HIPCHK(hipMemcpyAsync(io->hT, Wf(L.Hs) + (size_t)(L.T - 1) * M * 128, (size_t)M * 128 * 4,
+    HIPCHK(hipMemcpyAsync(io->hT, c.Wf(L.Hs) + (size_t)(L.T - 1) * M * 128, (size_t)M * 128 * 4,
                           hipMemcpyDeviceToDevice, st));
-  if (io->cT && (cqm_layout(L) & kCqmC)) HIPCHK(cqm_convert(Wf(L.Cst) + (size_t)L.T * M * 128, io->cT, L.B, P, 0, st));
+  if (io->cT && (c.plan.cqm & kCqmC)) HIPCHK(cqm_convert(c.Wf(L.Cst) + (size_t)L.T * M * 128, io->cT, L.B, L.P, 0, st));
   else if (io->cT)
-    HIPCHK(hipMemcpyAsync(io->cT, Wf(L.Cst) + (size_t)L.T * M * 128, (size_t)M * 128 * 4, hipMemcpyDeviceToDevice, st));
-  if (L.sc && io->core_hT)
-    HIPCHK(hipMemcpyAsync(io->core_hT, Wf(L.CH) + (size_t)L.T * L.B * 256, (size_t)L.B * 256 * 4,
-                          hipMemcpyDeviceToDevice, st));
-  if (L.sc && io->core_cT)
-    HIPCHK(hipMemcpyAsync(io->core_cT, Wf(L.CC) + (size_t)L.T * L.B * 256, (size_t)L.B * 256 * 4,
-                          hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(io->cT, c.Wf(L.Cst) + (size_t)L.T * M * 128, (size_t)M * 128 * 4, hipMemcpyDeviceToDevice, st));
+  if (L.sc && io->core_hT) HIPCHK(hipMemcpyAsync(io->core_hT, c.Wf(L.CH) + L.T * sB, sB * 4, hipMemcpyDeviceToDevice, st));
+  if (L.sc && io->core_cT) HIPCHK(hipMemcpyAsync(io->core_cT, c.Wf(L.CC) + L.T * sB, sB * 4, hipMemcpyDeviceToDevice, st));
   return AAA_OK;
+}
+
+template <typename T>
+int forward_impl(const Layout& L, const aaa_io* io, hipStream_t st, int phases, const float* reset) {
+  const CallCtx c(L, io, st, reset, AAA_TIMER_TAIL_FWD);
+  const bool core = (phases & AAA_FWD_CORE) != 0;
+  if (const int rc = vision_forward<T>(c)) return rc;
+  if (const int rc = state_in<T>(c, core)) return rc;
+  // (no CORE, aaa_forward_phases: aaa_core_import has left the recurrence's products in Gt / Cst / Hs / XH)
+  if (core)
+    if (const int rc = core_forward<T>(c)) return rc;
+  return forward_tail(c);
 }
 
 template int pack_impl<float>(const Layout&, const float*, char*, hipStream_t);

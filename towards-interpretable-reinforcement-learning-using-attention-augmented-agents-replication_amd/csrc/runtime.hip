@@ -174,8 +174,6 @@ int aaa_timing_stats(int kind, aaa_timer_stats* out) {
   return rc;
 }
 
-static int core_gate_bytes(const Layout& L);   // bytes of one stored gate activation (below)
-
 int aaa_workspace_region(const aaa_cfg* cfg, int region, size_t* offset, size_t* bytes) {
   if (!offset || !bytes) return fail(AAA_E_ARG, "workspace_region: NULL output");
   Layout L;
@@ -224,34 +222,20 @@ int aaa_workspace_region(const aaa_cfg* cfg, int region, size_t* offset, size_t*
     case AAA_WS_QUERY_HIDDEN1:
       if (!L.sc) break;
       *offset = L.q2s; *bytes = F * (size_t)L.qd * 4; return AAA_OK;
-    // the fp32 recurrence's operands and cotangents (row-major fp32 only: a checker's fp64 reference of the
-    // ConvLSTM GEMMs reads the kernels' own inputs here)
-    case AAA_WS_CORE_XH:
-    case AAA_WS_CORE_DO:
-    case AAA_WS_CORE_DX: {
-      if (L.dt != AAA_F32 || cqm_layout(L)) break;
-      const size_t M = (size_t)L.B * L.P;
-      if (region == AAA_WS_CORE_XH) { *offset = L.XH; *bytes = (size_t)(L.T + 1) * M * 192 * 4; }
-      else if (region == AAA_WS_CORE_DO) { *offset = L.dO; *bytes = F * L.P * 128 * 4; }
-      else { *offset = L.dY2; *bytes = F * L.P * 64 * 4; }
-      return AAA_OK;
-    }
-    // the bf16 recurrence's buffers as build_layout lays them out (bf16 only, every geometry: the slices of
-    // _C / _GATES / _DO are channel-quad-major where aaa_core_layout's mask says so), each a buffer of its own
-    case AAA_BF16_WS_XH:
-    case AAA_BF16_WS_C:
-    case AAA_BF16_WS_GATES:
-    case AAA_BF16_WS_DO:
-    case AAA_BF16_WS_DZ:
-    case AAA_BF16_WS_DX: {
-      if (L.dt != AAA_BF16) break;
-      const size_t M = (size_t)L.B * L.P;
-      if (region == AAA_BF16_WS_XH) { *offset = L.XH; *bytes = (size_t)(L.T + 1) * M * 192 * 2; }
+    // The recurrence's buffers as the kernels store them, each a buffer of its own (a checker's fp64 reference of the
+    // ConvLSTM GEMMs reads their own operands and cotangents here).  AAA_WS_CORE_*: fp32 configs only, all row-major.
+    // AAA_BF16_WS_*: bf16 configs only; _C / _GATES / _DO channel-quad-major where aaa_core_layout's mask says so.
+    case AAA_WS_CORE_XH: case AAA_WS_CORE_DO: case AAA_WS_CORE_DX:
+    case AAA_BF16_WS_XH: case AAA_BF16_WS_C: case AAA_BF16_WS_GATES:
+    case AAA_BF16_WS_DO: case AAA_BF16_WS_DZ: case AAA_BF16_WS_DX: {
+      if ((region <= AAA_WS_CORE_DX) != (L.dt == AAA_F32)) break;
+      const size_t M = (size_t)L.B * L.P, e = L.esz;
+      if (region == AAA_WS_CORE_XH || region == AAA_BF16_WS_XH) { *offset = L.XH; *bytes = (size_t)(L.T + 1) * M * 192 * e; }
+      else if (region == AAA_WS_CORE_DO || region == AAA_BF16_WS_DO) { *offset = L.dO; *bytes = F * L.P * 128 * 4; }
+      else if (region == AAA_WS_CORE_DX || region == AAA_BF16_WS_DX) { *offset = L.dY2; *bytes = F * L.P * 64 * e; }
       else if (region == AAA_BF16_WS_C) { *offset = L.Cst; *bytes = (size_t)(L.T + 1) * M * 128 * 4; }
-      else if (region == AAA_BF16_WS_GATES) { *offset = L.Gt; *bytes = F * L.P * 512 * core_gate_bytes(L); }
-      else if (region == AAA_BF16_WS_DO) { *offset = L.dO; *bytes = F * L.P * 128 * 4; }
       else if (region == AAA_BF16_WS_DZ) { *offset = L.dZ; *bytes = F * L.P * 512 * 2; }
-      else { *offset = L.dY2; *bytes = F * L.P * 64 * 2; }
+      else { *offset = L.Gt; *bytes = F * L.P * 512 * recur_plan(L, false).gate_bytes; }
       return AAA_OK;
     }
     default: break;
@@ -263,8 +247,9 @@ int aaa_core_layout(const aaa_cfg* cfg, int* gate_bytes, int* cqm_mask) {
   if (!gate_bytes || !cqm_mask) return fail(AAA_E_ARG, "core_layout: NULL output");
   Layout L;
   if (int r = build_layout(cfg, L)) return r;
-  *gate_bytes = core_gate_bytes(L);
-  *cqm_mask = cqm_layout(L);
+  const RecurPlan plan = recur_plan(L, false);
+  *gate_bytes = plan.gate_bytes;
+  *cqm_mask = plan.cqm;
   return AAA_OK;
 }
 
@@ -323,24 +308,13 @@ static int check_io(const Layout& L, const aaa_io* io, bool bwd) {
   return AAA_OK;
 }
 
-int aaa_forward(const aaa_cfg* cfg, const aaa_io* io, hipStream_t stream) {
-  Layout L;
-  int r = build_layout(cfg, L);
-  if (r) return r;
-  if ((r = check_device())) return r;
-  if ((r = check_io(L, io, false))) return r;
-  if (!(cfg->flags & AAA_FLAG_DEFER_STRANDED) && (r = pair_check())) return r;
-  return L.dt == AAA_BF16 ? forward_impl<__bf16>(L, io, stream, AAA_FWD_ALL)
-                          : forward_impl<float>(L, io, stream, AAA_FWD_ALL);
-}
-
 int aaa_forward_phases(const aaa_cfg* cfg, const aaa_io* io, int phases, hipStream_t stream) {
   Layout L;
   int r = build_layout(cfg, L);
   if (r) return r;
   if (phases != AAA_FWD_ALL && phases != (AAA_FWD_VISION | AAA_FWD_TAIL))
     return fail(AAA_E_ARG, "forward phases %d: AAA_FWD_ALL or AAA_FWD_VISION | AAA_FWD_TAIL", phases);
-  if (!(phases & AAA_FWD_CORE) && cqm_layout(L))
+  if (!(phases & AAA_FWD_CORE) && recur_plan(L, false).cqm)
     return fail(AAA_E_ARG, "skipping the core: not with channel-quad-major slices (the frame-resident BPTT's)");
   if ((r = check_device())) return r;
   if ((r = check_io(L, io, false))) return r;
@@ -348,26 +322,33 @@ int aaa_forward_phases(const aaa_cfg* cfg, const aaa_io* io, int phases, hipStre
   return L.dt == AAA_BF16 ? forward_impl<__bf16>(L, io, stream, phases) : forward_impl<float>(L, io, stream, phases);
 }
 
+int aaa_forward(const aaa_cfg* cfg, const aaa_io* io, hipStream_t stream) {
+  return aaa_forward_phases(cfg, io, AAA_FWD_ALL, stream);
+}
+
 // The recurrence's per-step products in the workspace (rt_core.hip
 // build_layout): Gt [T][M][512] (fp32, or fp16 on the bf16 path's gate
 // storage), Cst [T+1][M][128] fp32 (slot t+1 = c_t), Hs [T][M][128] fp32 (= h_t;
 // fp32 path only), XH [T+1][M][192] (channels 64.. of slot t+1 = h_t, in the
 // operand type: the bf16 path's only copy of h_t).
-static int core_xfer_check(const aaa_cfg* cfg, Layout& L, const void* ws, int t0, int n) {
+// *ge <- bytes of one stored gate activation
+static int core_xfer_check(const aaa_cfg* cfg, Layout& L, const void* ws, int t0, int n, size_t* ge) {
   int r = build_layout(cfg, L);
   if (r) return r;
-  if (cqm_layout(L)) return fail(AAA_E_ARG, "core export/import: channel-quad-major slices unsupported");
+  const RecurPlan plan = recur_plan(L, false);
+  *ge = plan.gate_bytes;
+  if (plan.cqm) return fail(AAA_E_ARG, "core export/import: channel-quad-major slices unsupported");
   if (!ws || t0 < 0 || n < 1 || t0 + n > L.T) return fail(AAA_E_ARG, "core export/import: steps [%d, %d) of T=%d", t0, t0 + n, L.T);
   return check_device();
 }
-static int core_gate_bytes(const Layout& L) { return L.dt == AAA_BF16 && gates_f16(L.dt, L.B * L.P) ? 2 : 4; }
 
 int aaa_core_elem_bytes(const aaa_cfg* cfg, int* gate_bytes, int* h_bytes) {
   if (!gate_bytes || !h_bytes) return fail(AAA_E_ARG, "core_elem_bytes: NULL output");
   Layout L;
   if (int r = build_layout(cfg, L)) return r;
-  const bool ok = !cqm_layout(L);   // channel-quad-major slices: no export / import (0 bytes)
-  *gate_bytes = ok ? core_gate_bytes(L) : 0;
+  const RecurPlan plan = recur_plan(L, false);
+  const bool ok = !plan.cqm;   // channel-quad-major slices: no export / import (0 bytes)
+  *gate_bytes = ok ? plan.gate_bytes : 0;
   *h_bytes = ok ? L.esz : 0;
   return AAA_OK;
 }
@@ -375,9 +356,10 @@ int aaa_core_elem_bytes(const aaa_cfg* cfg, int* gate_bytes, int* h_bytes) {
 int aaa_core_export(const aaa_cfg* cfg, const void* workspace, int t0, int n, void* gates, float* c, void* h,
                     hipStream_t st) {
   Layout L;
-  if (int r = core_xfer_check(cfg, L, workspace, t0, n)) return r;
+  size_t ge;
+  if (int r = core_xfer_check(cfg, L, workspace, t0, n, &ge)) return r;
   const char* ws = (const char*)workspace;
-  const size_t M = (size_t)L.B * L.P, ge = core_gate_bytes(L);
+  const size_t M = (size_t)L.B * L.P;
   if (gates) HIPCHK(hipMemcpyAsync(gates, ws + L.Gt + (size_t)t0 * M * 512 * ge, (size_t)n * M * 512 * ge, hipMemcpyDeviceToDevice, st));
   if (c) HIPCHK(hipMemcpyAsync(c, ws + L.Cst + (size_t)(t0 + 1) * M * 128 * 4, (size_t)n * M * 128 * 4, hipMemcpyDeviceToDevice, st));
   if (h && L.esz == 4)
@@ -391,10 +373,11 @@ int aaa_core_export(const aaa_cfg* cfg, const void* workspace, int t0, int n, vo
 int aaa_core_import(const aaa_cfg* cfg, void* workspace, int t0, int n, const void* gates, const float* c,
                     const void* h, hipStream_t st) {
   Layout L;
-  if (int r = core_xfer_check(cfg, L, workspace, t0, n)) return r;
+  size_t ge;
+  if (int r = core_xfer_check(cfg, L, workspace, t0, n, &ge)) return r;
   if (!gates || !c || !h) return fail(AAA_E_ARG, "core import: gates, c and h are required");
   char* ws = (char*)workspace;
-  const size_t M = (size_t)L.B * L.P, ge = core_gate_bytes(L);
+  const size_t M = (size_t)L.B * L.P;
   HIPCHK(hipMemcpyAsync(ws + L.Gt + (size_t)t0 * M * 512 * ge, gates, (size_t)n * M * 512 * ge, hipMemcpyDeviceToDevice, st));
   HIPCHK(hipMemcpyAsync(ws + L.Cst + (size_t)(t0 + 1) * M * 128 * 4, c, (size_t)n * M * 128 * 4, hipMemcpyDeviceToDevice, st));
   if (L.esz == 4) {
