@@ -714,6 +714,32 @@ size_t aaa_actor_core_workspace_bytes(const aaa_cfg* cfg);
 int aaa_actor_step_core(const aaa_cfg* cfg, const aaa_actor_io* io, const aaa_actor_core_io* core,
                         hipStream_t stream);
 
+/* ---- actor: a checker's view of the step's workspace (added after ABI 12 without a bump:
+ * additive, probe by name) ----
+ * Where the chain's stages hand their products to the next, inside the
+ * workspace of aaa_actor_workspace_bytes() -- or, for a cfg with
+ * AAA_FLAG_STATEFUL_CORE, of aaa_actor_core_workspace_bytes() -- as (offset,
+ * bytes), valid after a step, all fp32, rows of frame b first:
+ *   AAA_ACT_WS_X       (B, P, 64)   conv2's output, the ConvLSTM's x
+ *   AAA_ACT_WS_HS      (B, P, 128)  h_t as the readout reads it
+ *   AAA_ACT_WS_HID1    (B, 512)     relu(answer_processor.0)
+ *   AAA_ACT_WS_AO      (B, 256)     answer_processor.2
+ *   AAA_ACT_WS_LH      (B, 256)     the LSTMCell's h_t, the heads' input
+ *   AAA_ACT_WS_LOGITS  (B, P, nq)   the attention logits K.Q
+ *   AAA_ACT_WS_ANSWER  (B, ans_ld)  [readout | Q | prev_reward | prev_action | 0],
+ *                                   ans_ld = 256 nq + 2 rounded up to 8
+ *   AAA_ACT_WS_QT      (B, nq*72)   stateful core: this step's Q_t
+ *   AAA_ACT_WS_Q1      (B, 128)     stateful core: relu(query.model.0)
+ *   AAA_ACT_WS_Q2      (B, nq*72)   stateful core: relu(query.model.2)
+ * Offsets are 256-byte aligned and the regions disjoint.  Touches no device.
+ * AAA_E_ARG for every cfg the step itself refuses, for an unknown region and
+ * for _QT / _Q1 / _Q2 on a cfg without the stateful core. */
+enum aaa_act_ws_region {
+  AAA_ACT_WS_X = 0, AAA_ACT_WS_HS = 1, AAA_ACT_WS_HID1 = 2, AAA_ACT_WS_AO = 3, AAA_ACT_WS_LH = 4,
+  AAA_ACT_WS_LOGITS = 5, AAA_ACT_WS_ANSWER = 6, AAA_ACT_WS_QT = 7, AAA_ACT_WS_Q1 = 8, AAA_ACT_WS_Q2 = 9
+};
+int aaa_actor_workspace_region(const aaa_cfg* cfg, int region, size_t* offset, size_t* bytes);
+
 /* ---- actor: recording unrolls (added after ABI 11 without a bump: additive, probe by name) ----
  * Two small calls around an actor step (aaa_actor_step, aaa_actor_step_core or
  * aaa_forward with T = 1) assemble the time-major unroll the learner trains

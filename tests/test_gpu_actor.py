@@ -247,13 +247,15 @@ def test_actor_chain_matches_learner_forward(cuda, H, W, B, nq, u8):
 
 
 def test_actor_chain_refuses_unsupported(cuda):
-    """bf16, stateful-core, T > 1 and B > 16 configurations are refused with AAA_E_ARG
-    (they run on aaa_forward), never silently computed."""
+    """bf16, stateful-core, T > 1 and B > 16 configurations, and a 514x256 frame (a 65x32 grid: 130 readout
+    chunks, past kActMaxChunks), are refused with AAA_E_ARG (they run on aaa_forward), never silently computed."""
     import ctypes
     from aaa_amd import _native as N
     lib = N.load()
+    assert N.grid(514, 256) == (65, 32)
     for cfg in (N.Cfg(1, 1, 84, 84, 4, 18, N.BF16, 0), N.Cfg(1, 1, 84, 84, 4, 18, N.F32, N.FLAG_STATEFUL_CORE),
-                N.Cfg(1, 2, 84, 84, 4, 18, N.F32, 0), N.Cfg(17, 1, 84, 84, 4, 18, N.F32, 0)):
+                N.Cfg(1, 2, 84, 84, 4, 18, N.F32, 0), N.Cfg(17, 1, 84, 84, 4, 18, N.F32, 0),
+                N.Cfg(1, 1, 514, 256, 4, 18, N.F32, 0)):
         assert lib.aaa_actor_workspace_bytes(ctypes.byref(cfg)) == 0
         io = N.ActorIO()
         assert lib.aaa_actor_step(ctypes.byref(cfg), ctypes.byref(io), None) == -1

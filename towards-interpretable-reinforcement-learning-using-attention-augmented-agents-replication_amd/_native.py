@@ -43,6 +43,7 @@ EXPORTS = (
     "aaa_rmsprop_step",
     "aaa_unroll_begin", "aaa_unroll_record",
     "aaa_core_layout",
+    "aaa_actor_workspace_region",
 )
 # include/aaa.h enum aaa_timer
 TIMER_FWD_STEP, TIMER_BPTT_STEP, TIMER_CORE_WGRAD, TIMER_ATTN_FWD, TIMER_ATTN_BWD = 0, 1, 2, 3, 4
@@ -72,6 +73,8 @@ WS_CORE_XH, WS_CORE_DO, WS_CORE_DX = 3, 4, 5   # fp32 configs only (ABI 11)
 # the bf16 recurrence's buffers as stored, bf16 configs only (include/aaa.h AAA_BF16_WS_*; aaa_core_layout)
 BF16_WS_XH, BF16_WS_C, BF16_WS_GATES, BF16_WS_DO, BF16_WS_DZ, BF16_WS_DX = range(24, 30)
 CQM_C, CQM_G, CQM_DO = 1, 2, 4   # aaa_core_layout's mask: which of _C / _GATES / _DO are channel-quad-major
+# include/aaa.h enum aaa_act_ws_region (aaa_actor_workspace_region): the actor chain's hand-offs
+ACT_WS = {"X": 0, "HS": 1, "HID1": 2, "AO": 3, "LH": 4, "LOGITS": 5, "ANSWER": 6, "QT": 7, "Q1": 8, "Q2": 9}
 
 
 class TimerStats(ctypes.Structure):
@@ -227,6 +230,8 @@ def load(path: str = LIB_PATH):
             "aaa_core_layout": (I, [ctypes.POINTER(Cfg), ctypes.POINTER(I), ctypes.POINTER(I)]),
             "aaa_workspace_region": (I, [ctypes.POINTER(Cfg), I, ctypes.POINTER(ctypes.c_size_t),
                                          ctypes.POINTER(ctypes.c_size_t)]),
+            "aaa_actor_workspace_region": (I, [ctypes.POINTER(Cfg), I, ctypes.POINTER(ctypes.c_size_t),
+                                               ctypes.POINTER(ctypes.c_size_t)]),
             "aaa_reinforce": (I, [I, I, I, P, P, P, ctypes.c_double, P, P, P, P]),
             "aaa_vtrace": (I, [ctypes.POINTER(VtraceDesc), ctypes.POINTER(VtraceIO), P]),
             "aaa_sample_actions": (I, [I, I, P, ctypes.c_ulonglong, P, P, P, P, P]),

@@ -744,7 +744,8 @@ int aaa_unroll_record(const aaa_unroll_desc* d, const aaa_unroll_io* io, hipStre
 // the readout's chunk partials and the answer row (actor.h).
 // The stateful-core entry (core = true) adds Q_t (B, nq*72) and the query MLP's two hidden rows.
 constexpr int kActRegions = 13;
-static int actor_layout(const aaa_cfg* cfg, Layout& L, size_t off[kActRegions], size_t* total, bool core = false) {
+static int actor_layout(const aaa_cfg* cfg, Layout& L, size_t off[kActRegions], size_t* total, bool core = false,
+                        size_t* bytes = nullptr) {
   int r = build_layout(cfg, L);
   if (r) return r;
   const char* who = core ? "actor_step_core" : "actor_step";
@@ -765,6 +766,8 @@ static int actor_layout(const aaa_cfg* cfg, Layout& L, size_t off[kActRegions], 
                                   qc * B * L.qd * 4, qc * B * 128 * 4, qc * B * L.qd * 4};
   size_t o = 0;
   for (int i = 0; i < kActRegions; ++i) { off[i] = o; o = al256(o + sz[i]); }
+  if (bytes)
+    for (int i = 0; i < kActRegions; ++i) bytes[i] = sz[i];
   *total = o;
   return AAA_OK;
 }
@@ -779,6 +782,22 @@ size_t aaa_actor_core_workspace_bytes(const aaa_cfg* cfg) {
   Layout L;
   size_t off[kActRegions], tot = 0;
   return actor_layout(cfg, L, off, &tot, true) ? 0 : tot;
+}
+
+// Checker-only view of that layout (include/aaa.h enum aaa_act_ws_region): the regions a stage hands to the next.
+// Host arithmetic only; refused exactly where the step is (actor_layout), the layout chosen by the cfg's flag.
+int aaa_actor_workspace_region(const aaa_cfg* cfg, int region, size_t* offset, size_t* bytes) {
+  if (!cfg || !offset || !bytes) return fail(AAA_E_ARG, "actor_workspace_region: NULL argument");
+  static const int slot[] = {0, 1, 2, 3, 4, 7, 9, 10, 11, 12};   // AAA_ACT_WS_X .. _Q2 -> actor_layout's off[]
+  const bool core = (cfg->flags & AAA_FLAG_STATEFUL_CORE) != 0;
+  Layout L;
+  size_t off[kActRegions], sz[kActRegions], tot = 0;
+  if (int r = actor_layout(cfg, L, off, &tot, core, sz)) return r;
+  if (region < AAA_ACT_WS_X || region > AAA_ACT_WS_Q2 || (region >= AAA_ACT_WS_QT && !core))
+    return fail(AAA_E_ARG, "actor_workspace_region: region %d not computed by this cfg", region);
+  *offset = off[slot[region]];
+  *bytes = sz[slot[region]];
+  return AAA_OK;
 }
 
 static int actor_step_impl(const aaa_cfg* cfg, const aaa_actor_io* io, const aaa_actor_core_io* core, bool is_core,

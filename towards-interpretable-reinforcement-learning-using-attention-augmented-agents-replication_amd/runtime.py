@@ -516,6 +516,18 @@ class ActorRunner:
     def state_shape(self):
         return (self.B, self.h, self.w, 128)
 
+    def region(self, name: str, workspace):
+        """A stage's hand-off inside ``workspace`` after a step (aaa_actor_workspace_region; for checkers): a
+        float32 view with one leading row per frame -- "X" (B, P, 64), "HS" (B, P, 128), "HID1" (B, 512), "AO" /
+        "LH" (B, 256), "LOGITS" (B, P, nq), "ANSWER" (B, ans_ld) and, on a stateful-core runner, "QT" / "Q2"
+        (B, nq*72) and "Q1" (B, 128)."""
+        off, nb = ctypes.c_size_t(), ctypes.c_size_t()
+        N.check(self.lib.aaa_actor_workspace_region(ctypes.byref(self.cfg), N.ACT_WS[name], ctypes.byref(off),
+                                                    ctypes.byref(nb)), "actor_workspace_region")
+        flat = workspace[off.value:off.value + nb.value].view(torch.float32)
+        inner = {"X": (self.P, 64), "HS": (self.P, 128), "LOGITS": (self.P, self.nq)}.get(name, (-1,))
+        return flat.view(self.B, *inner)
+
     def pack(self, flat_params, packed):
         assert flat_params.dtype == torch.float32 and flat_params.is_contiguous()
         assert flat_params.numel() == self.n_params, (flat_params.numel(), self.n_params)
