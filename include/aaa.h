@@ -89,6 +89,17 @@ typedef struct aaa_cfg {
  * entry (see aaa_pair_status): the caller checks them itself after the
  * iteration, e.g. through aaa_pair_flag and the guarded optimizer. */
 #define AAA_FLAG_DEFER_STRANDED 4
+/* (8 is not a flag: it stays refused.)
+ * bf16 cfgs: episode-start masks (aaa_forward_resets / aaa_backward_resets).
+ * The workspace grows by one region appended behind every other,
+ * AAA_BF16_WS_HR: (T, B, P, 128) bf16, h_t as the attention readout reads it
+ * under a mask -- the h half of XH slot t+1 then holds zeros for the rows that
+ * start an episode at step t+1, which is the operand the next step's conv and
+ * the weight gradient read.  Packed bytes, regions 0..29 and aaa_core_layout
+ * are what they are without the flag, and a call without a mask launches
+ * exactly what the unflagged cfg launches (the readout reads XH; HR stays
+ * unwritten).  Accepted and without effect on an fp32 cfg. */
+#define AAA_FLAG_BF16_RESETS 16
 
 typedef struct aaa_io {
   /* inputs */
@@ -221,15 +232,26 @@ int aaa_backward(const aaa_cfg* cfg, const aaa_io* io, int phases, hipStream_t s
  * reset == NULL is exactly aaa_forward_phases / aaa_backward.
  * After the forward, AAA_WS_CORE_XH slot t holds zeros in the h half of the
  * rows with reset[t]: the operand the kernels really used.
- * Refused before the device is touched: AAA_E_ARG for a bf16 cfg with a mask
- * (its readout reads h_t from the [x | h] operand slots, which a reset
- * zeroes: cut bf16 unrolls at episode ends) and for a forward phase mask
- * without AAA_FWD_CORE together with a mask; AAA_E_ALIGN for a mask that is
- * not 16-byte aligned.
+ * Refused before the device is touched: AAA_E_ARG for a bf16 cfg without
+ * AAA_FLAG_BF16_RESETS with a mask (its readout reads h_t from the [x | h]
+ * operand slots, which a reset zeroes: set the flag, or cut bf16 unrolls at
+ * episode ends) and for a forward phase mask without AAA_FWD_CORE together
+ * with a mask; AAA_E_ALIGN for a mask that is not 16-byte aligned.
  * With a mask the production fp32 frame-group kernels run their mask
  * variants (forward: G = 8 pre-split and G = 4; BPTT: G = 8 with dx fused);
  * every other fp32 dispatch takes the per-step kernels.  The timer variants
- * of AAA_TIMER_FWD_STEP / AAA_TIMER_BPTT_STEP then end in ", resets". */
+ * of AAA_TIMER_FWD_STEP / AAA_TIMER_BPTT_STEP then end in ", resets".
+ * bf16 with AAA_FLAG_BF16_RESETS: every h_t is also stored in AAA_BF16_WS_HR
+ * slot t, bit for bit the value the next step's conv reads, and the readout
+ * (forward and backward) reads it there.  A masked call runs the
+ * single-workgroup frame-resident forward's mask variant where the forward's
+ * rule gives one workgroup per frame, behind it the single-workgroup
+ * frame-resident BPTT's mask variant where AAA_FRAMES_BWD's rule gives 1, and
+ * the per-step kernels everywhere else: the paired and band-mode kernels are
+ * never launched under a mask.  aaa_core_layout keeps describing the call
+ * without a mask; a masked call keeps _C / _GATES / _DO row-major wherever
+ * the plan sends its BPTT to the per-step chain (where the unmasked call
+ * would run a paired or band-mode kernel, or AAA_FRAMES_BWD gives 0). */
 int aaa_forward_resets(const aaa_cfg* cfg, const aaa_io* io, int phases, const float* reset, hipStream_t stream);
 int aaa_backward_resets(const aaa_cfg* cfg, const aaa_io* io, int phases, const float* reset, hipStream_t stream);
 
@@ -353,12 +375,19 @@ int aaa_pair_flag_at(float* dst, int* base, hipStream_t stream);
  *   AAA_BF16_WS_GATES  (T, M, 512) post-activation gates in the gate storage
  *                      type (aaa_core_layout: fp16, or fp32); after the forward;
  *   AAA_BF16_WS_DO     (T, M, 128) fp32: the readout's cotangent of h_t; after
- *                      AAA_BWD_HEAD;
+ *                      AAA_BWD_HEAD (aaa_backward_resets with a mask on the
+ *                      per-step BPTT chain: its AAA_BWD_CORE then leaves the
+ *                      raw dgrad dh_{t-1} in slots t >= 1, each consumed
+ *                      before it is overwritten);
  *   AAA_BF16_WS_DZ     (T, M, 512) bf16, row-major, column 4*ch + gate: the gate
  *                      pre-activations' cotangent dZ_t, the dgrad's and the
  *                      weight gradient's operand; after AAA_BWD_CORE;
  *   AAA_BF16_WS_DX     (T, M, 64) bf16, row-major: the cotangent of conv2's
- *                      output x_t; after AAA_BWD_CORE.
+ *                      output x_t; after AAA_BWD_CORE;
+ *   AAA_BF16_WS_HR     (T, M, 128) bf16, row-major: h_t as the readout reads it
+ *                      under an episode-start mask; AAA_FLAG_BF16_RESETS only
+ *                      (AAA_E_ARG without it), the last region of the
+ *                      workspace, written by aaa_forward_resets with a mask.
  * aaa_core_layout reports the gate storage size in bytes (2 or 4) and which of
  * _C / _GATES / _DO keep their slices channel-quad-major: bit 0 (1) _C, bit 1
  * (2) _GATES, bit 2 (4) _DO; 0 = all row-major (pixel-major, channel fastest;
@@ -381,7 +410,8 @@ enum aaa_ws_region {
   AAA_WS_TAIL_DAO = 19, AAA_WS_TAIL_DAOX = 20, AAA_WS_TAIL_DQUERY = 21, AAA_WS_TAIL_DQ2 = 22,
   AAA_WS_TAIL_DQ1 = 23,
   AAA_BF16_WS_XH = 24, AAA_BF16_WS_C = 25, AAA_BF16_WS_GATES = 26, AAA_BF16_WS_DO = 27, AAA_BF16_WS_DZ = 28,
-  AAA_BF16_WS_DX = 29
+  AAA_BF16_WS_DX = 29,
+  AAA_BF16_WS_HR = AAA_BF16_WS_DX + 1   /* 30: not one of the six checker regions above (AAA_FLAG_BF16_RESETS) */
 };
 int aaa_workspace_region(const aaa_cfg* cfg, int region, size_t* offset, size_t* bytes);
 int aaa_core_layout(const aaa_cfg* cfg, int* gate_bytes, int* cqm_mask);
@@ -608,7 +638,8 @@ int aaa_reinforce(int T, int B, int A, const float* logits, const int* actions, 
  * - entropy_cost l2).  An action outside [0, A) reads nothing outside its row
  * and makes that row's outputs NaN.  A done inside the unroll cuts the return
  * only; aaa_forward carries the recurrent state across it, and
- * aaa_forward_resets / aaa_backward_resets (fp32) cut the state with the mask
+ * aaa_forward_resets / aaa_backward_resets (fp32; bf16 with
+ * AAA_FLAG_BF16_RESETS) cut the state with the mask
  * reset[t] = done[t-1].  Every pointer is device memory; dlogits and dvalues
  * must be 16-byte aligned. */
 typedef struct aaa_vtrace_desc {

@@ -63,6 +63,7 @@ IO_FIELDS = ("params", "packed", "basis", "frames", "prev_reward", "prev_action"
 FLAG_STATEFUL_CORE = 1
 FLAG_FRAMES_U8 = 2
 FLAG_DEFER_STRANDED = 4
+FLAG_BF16_RESETS = 16   # bf16 cfgs: episode-start masks, one more workspace region (BF16_WS_HR); 8 is no flag
 # include/aaa.h enum aaa_ws_region
 WS_ANSWER_HIDDEN, WS_QUERY_HIDDEN0, WS_QUERY_HIDDEN1 = 0, 1, 2
 WS_CORE_XH, WS_CORE_DO, WS_CORE_DX = 3, 4, 5   # fp32 configs only (ABI 11)
@@ -72,6 +73,7 @@ WS_CORE_XH, WS_CORE_DO, WS_CORE_DX = 3, 4, 5   # fp32 configs only (ABI 11)
  WS_TAIL_DQ1) = range(6, 24)
 # the bf16 recurrence's buffers as stored, bf16 configs only (include/aaa.h AAA_BF16_WS_*; aaa_core_layout)
 BF16_WS_XH, BF16_WS_C, BF16_WS_GATES, BF16_WS_DO, BF16_WS_DZ, BF16_WS_DX = range(24, 30)
+BF16_WS_HR = 30   # (T, B*h*w, 128) bf16: h_t for the readout of a masked call; FLAG_BF16_RESETS only
 CQM_C, CQM_G, CQM_DO = 1, 2, 4   # aaa_core_layout's mask: which of _C / _GATES / _DO are channel-quad-major
 # include/aaa.h enum aaa_act_ws_region (aaa_actor_workspace_region): the actor chain's hand-offs
 ACT_WS = {"X": 0, "HS": 1, "HID1": 2, "AO": 3, "LH": 4, "LOGITS": 5, "ANSWER": 6, "QT": 7, "Q1": 8, "Q2": 9}

@@ -361,7 +361,8 @@ class Agent(nn.Module):
     """Attention-augmented agent (attention.py:257-368) on the gfx950 HIP path."""
 
     def __init__(self, num_actions, hidden_size: int = 256, c_v: int = 120, c_k: int = 8, c_s: int = 64,
-                 num_queries: int = 4, *, grid=None, conv_dtype: str = "fp32", stateful_core: bool = False):
+                 num_queries: int = 4, *, grid=None, conv_dtype: str = "fp32", stateful_core: bool = False,
+                 resets: bool = False):
         super().__init__()
         if (hidden_size, c_v, c_k, c_s) != (256, 120, 8, 64):
             raise ValueError("hidden_size/c_v/c_k/c_s are hard-coded elsewhere in the reference "
@@ -374,6 +375,9 @@ class Agent(nn.Module):
         self.c_v, self.c_k, self.c_s, self.num_queries = c_v, c_k, c_s, num_queries
         self.num_actions = num_actions
         self.conv_dtype = conv_dtype
+        # bf16 agents: ``unroll(reset=)`` needs runners built with the episode-start flag (one more workspace
+        # region, AAA_FLAG_BF16_RESETS); fp32 agents take a mask anyway
+        self.resets = bool(resets)
         # the reference's else branch (attention.py:356-358): also taken whenever
         # a caller puts a tensor in ``prev_hidden``, exactly as the reference does
         self.stateful_core = bool(stateful_core)
@@ -447,8 +451,9 @@ class Agent(nn.Module):
         leaves the final state in ``vision.vision_lstm.prev_hidden``.
         ``reset`` (T, B) device tensor: rows with ``reset[t, b] != 0`` enter
         step t from the ``reset()`` state, as if ``agent.reset()`` had been
-        called for that row alone (fp32 agents; ``vtrace.episode_starts``
-        makes the mask from ``done``).  The backward cuts at the same places.
+        called for that row alone (fp32 agents, and bf16 agents built with
+        ``resets=True``; ``vtrace.episode_starts`` makes the mask from
+        ``done``).  The backward cuts at the same places.
         """
         logits, values, attn = self._step(X, prev_reward, prev_action, reset)
         self.last_attention = attn
@@ -553,6 +558,9 @@ class Agent(nn.Module):
         T, B, H, W, C = X.shape
         if C != 3:
             raise ValueError(f"frames must be (..., H, W, 3), got {tuple(X.shape)}")
+        if reset is not None and self.conv_dtype == "bf16" and not self.resets:
+            raise RuntimeError("aaa: a bf16 agent takes unroll(reset=) only when built with resets=True: "
+                               "Agent(..., conv_dtype=\"bf16\", resets=True)")
         params = self._param_list()
         stateful = self.stateful_core or self.prev_hidden is not None
         u8 = X.dtype == torch.uint8      # the environment's observation: cast in-kernel (AAA_FLAG_FRAMES_U8)
@@ -613,11 +621,12 @@ class Agent(nn.Module):
         return flat, packed
 
     def _runner(self, B, T, H, W, device, stateful=False, frames_u8=False):
-        key = (B, T, H, W, str(device), self.conv_dtype, bool(stateful), bool(frames_u8))
+        resets = self.resets and self.conv_dtype == "bf16"
+        key = (B, T, H, W, str(device), self.conv_dtype, bool(stateful), bool(frames_u8), resets)
         r = self._runners.get(key)
         if r is None:
             r = UnrollRunner(B, T, H, W, self.num_queries, self.num_actions, self.conv_dtype, device,
-                             stateful_core=stateful, frames_u8=frames_u8)
+                             stateful_core=stateful, frames_u8=frames_u8, resets=resets)
             self._runners[key] = r
         return r
 

@@ -125,22 +125,35 @@ hipError_t gate_fwd_zx(int M, const float* cprev, float* gates, float* cnext, fl
                        const float* zs = nullptr, int nsl = 0, size_t sls = 0, const float* bias = nullptr);
 // Episode-start masks (resets.hip).  rs: one step's mask row [B], frame b's rows are [b*rpb, (b+1)*rpb).
 // Zero ranges of the rows of frames with rs[b] != 0: w elements at element stride es, row pitch ld.
-struct ResetZero { float* p; int ld, w, es; };
-struct ResetZeros {
-  ResetZero r[4];
+// (TE: the ranges' element type -- fp32, or bf16 for the h half of the bf16 path's XH slots)
+template <typename TE> struct ResetZeroT { TE* p; int ld, w, es; };
+template <typename TE> struct ResetZerosT {
+  ResetZeroT<TE> r[4];
   int n = 0;
-  ResetZeros& add(float* p, int ld, int w, int es = 1) {
-    if (p) r[n++] = ResetZero{p, ld, w, es};
+  ResetZerosT& add(TE* p, int ld, int w, int es = 1) {
+    if (p) r[n++] = ResetZeroT<TE>{p, ld, w, es};
     return *this;
   }
 };
+using ResetZeros = ResetZerosT<float>;
 // the zero ranges, and (dst != null) dst[row][0..cw) = rs[b] ? 0 : src[row][0..cw) for every row
-hipError_t reset_rows(const float* rs, int B, int rpb, const ResetZeros& z, const float* src, float* dst, int cw,
+template <typename TE>
+hipError_t reset_rows(const float* rs, int B, int rpb, const ResetZerosT<TE>& z, const float* src, float* dst, int cw,
                       hipStream_t st);
 // after the gate backward of step t-1: frames with rs_in[b] (reset[t]) recomputed from dh = dO and a zero dc
 // carry, d f-gate = 0 for frames with rs_c[b] (reset[t-1]); rs_in null: the last step
+// (fp32; the bf16 path runs gate_bwd_resets below instead)
 hipError_t reset_gate_bwd(const float* rs_in, const float* rs_c, int M, int P, const float* dO, const float* gates,
                           const float* cprev, const float* ccur, float* dC, float* dz, hipStream_t st);
+// bf16: the whole gate backward of step t-1 under a mask, from the step GEMM's raw dgrad ``dh`` (or the last step's
+// dhT; null: none), with fp32 gate-bias partials per tile of bj pixels (part, or null) -- resets.hip
+template <typename TZ, typename GT>
+hipError_t gate_bwd_resets(int M, int bj, int P, const float* rs_in, const float* rs_c, const float* dO, const float* dh,
+                           const GT* gates, const float* cprev, const float* ccur, float* dC, TZ* dz, float* part,
+                           hipStream_t st);
+// bf16 under a mask: the h half of ``rows`` XH rows (h_t, before the next step's reset_rows zeroes the rows of an
+// episode start) -> the readout's copy, dense rows of 128 (AAA_BF16_WS_HR)
+hipError_t xh_to_hr(long rows, const __bf16* xh, __bf16* hr, hipStream_t st);
 hipError_t pack_f32(const F32Pack& p, hipStream_t st);
 // Channel-chunk-major copy of conv-GEMM rows (ConvGeo::cmaj): row r's K = taps x Cin
 // (tap-major) -> dst[r][(c / BK) * taps * BK + tap * BK + c % BK]

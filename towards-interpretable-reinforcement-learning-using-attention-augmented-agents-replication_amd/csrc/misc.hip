@@ -1239,7 +1239,10 @@ hipError_t attn_fwd(OSrc O, const float* S, const float* Q, const float* SQ, con
   const int sl = O.bf16 ? kAttnSlicesBf : sl_env > 0 ? sl_env : kAttnSlices;
   const size_t sh = (size_t)(P * nq + nq * 72 + sl * nq * 184) * sizeof(float);
   if (sh > 160 * 1024) return hipErrorInvalidValue;
-  if (O.bf16 ? (O.ld < 136 || O.ld % 8) : O.ld < 128 || O.ld % 4) return hipErrorInvalidValue;   // 16-B key loads
+  // 16-B key loads.  (bf16: every load of a row ends at channel 128 -- key_raw [0, 8), the V groups 8 + 4g + [0, 4),
+  // g < 30 -- so dense rows of 128, the masked bf16 calls' HR copy, are in range; the public component entries
+  // keep their own stricter pitch rule, rt_components.hip check_attn_bf16.)
+  if (O.bf16 ? (O.ld < 128 || O.ld % 8) : O.ld < 128 || O.ld % 4) return hipErrorInvalidValue;
   auto launch = [&](auto kern, auto* o) {
     if (sh > 64 * 1024)
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1281,7 +1284,9 @@ hipError_t attn_bwd(OSrc O, const float* S, const float* Q, const float* Am, con
   const int G = 7;   // k_attn_bwd's dQ position groups
   const size_t sh = (size_t)(2 * P * nq + nq * 184 + nq * 72 + 8 + G * nq * 72 + P * 8) * sizeof(float);
   if (sh > 160 * 1024) return hipErrorInvalidValue;
-  if (O.bf16 ? (O.ld < 136 || O.ld % 4) : O.ld < 128 || O.ld % 4) return hipErrorInvalidValue;
+  // (bf16: k_attn_bwd's last V piece is clamped to channels [120, 128) and k_attn_bwd_mfma loads through a
+  // descriptor over the frame's rows, so dense rows of 128 -- the masked bf16 calls' HR copy -- are in range)
+  if (O.bf16 ? (O.ld < 128 || O.ld % 8) : O.ld < 128 || O.ld % 4) return hipErrorInvalidValue;
   auto launch = [&](auto kern, auto* o) {
     if (sh > 64 * 1024)   // large grids (168x168: P = 441, nq = 8) use more than the default 64 KiB
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,

@@ -125,6 +125,10 @@ struct RecFwdParams {
   // GEMM column c -> pixel (colpp, -1 = padding column) and the top-left image
   // index of its 3x3 window (colhb); filled by convlstm_fwd_frames (rec_columns)
   short colpp[128], colhb[128];
+  // Episode starts (the RST variant of the single-workgroup kernel only): the (T, B) mask, and (T, B, P, 128)
+  // <- h_t for the readout, which under a mask cannot read it from XH
+  const float* reset = nullptr;
+  __bf16* HR = nullptr;
 };
 
 // Column order of the frame-resident GEMMs.  A B-fragment ds_read_b128 serves
@@ -222,9 +226,18 @@ __device__ uint64_t aaa_fw_stamps[1024 * 64 * 8];
 // x-part reads the neighbours' boundary rows into its halo rows (sc1 loads),
 // like the G = 2 hand-off.  The bands of a frame get block indices of equal
 // residue mod 8 (one XCD under round-robin placement).
-template <typename GT, int G = 1, int ABL = 0, bool BAND = false>
+//
+// RST (G = 1, not BAND: one workgroup owns the frame): episode starts inside the launch.  reset[t][b] != 0 means
+// frame b enters step t from the reset() state.  The mask is frame-uniform, so every branch on it is
+// workgroup-uniform.  After step t the kernel also stores h_t in HR slot t (the readout's copy); where
+// reset[t+1][b], XH slot t+1's h half gets zeros instead of h_t (the operand of step t+1 and of the weight
+// gradient), and the h image's interior and the lane-native c copy are zeroed -- exactly the state a fresh launch
+// starts from: the h-part of step t+1 runs on zeros, its cell update reads c = 0.  Cst slot t+1 keeps the true c_t.
+// reset[0][b]: the host zeroes XH slot 0's h half before the launch; Cst slot 0 is read as 0 here.
+template <typename GT, int G = 1, int ABL = 0, bool BAND = false, bool RST = false>
 __global__ void __launch_bounds__(256) k_convlstm_fwd_frames(RecFwdParams<GT> p) {
   static_assert(!BAND || G == 1, "band mode splits pixels, not channels");
+  static_assert(!RST || (G == 1 && !BAND && ABL == 0), "the mask form exists only where one workgroup owns a frame");
   constexpr int NRB = 4 / G, GCH = 8 * NRB;     // row blocks and channels per wave
   constexpr int GTP = GCH * 8 + 16, CHP = GCH * 4 + 16;   // staging pixel pitches (gates fp16x4, c / h fp32)
   __shared__ __attribute__((aligned(16))) unsigned char xim[kRecXB];
@@ -293,6 +306,8 @@ __global__ void __launch_bounds__(256) k_convlstm_fwd_frames(RecFwdParams<GT> p)
   };
   dma_x(0, false);
   // cell state c_0 (Cst slot 0) into the lane-native LDS copy
+  bool rst0 = false;   // RST: the frame starts an episode at step 0 (c_0 read as 0)
+  if constexpr (RST) rst0 = p.reset[b] != 0.f;
 #pragma unroll
   for (int rb = 0; rb < NRB; ++rb)
 #pragma unroll
@@ -302,7 +317,7 @@ __global__ void __launch_bounds__(256) k_convlstm_fwd_frames(RecFwdParams<GT> p)
         const int pp = BAND ? (cb * 32 + r32 < Pb ? pix0 + cb * 32 + r32 : -1) : p.colpp[cb * 32 + r32];
         const int ch = cbase + 8 * rb + 2 * g + hh;
         cw[(rb * 16 + cb * 4 + g) * 64] =
-            pp >= 0 ? p.Cst[(size_t)b * P * 128 + slc4(pp, ch, P, p.cqm & kCqmC)] : 0.f;
+            pp >= 0 && !(RST && rst0) ? p.Cst[(size_t)b * P * 128 + slc4(pp, ch, P, p.cqm & kCqmC)] : 0.f;
       }
   __syncthreads();   // h image zeroed
   {  // h_0 (slot 0, channels 64..191) into the image (band mode: the band's rows and its halo rows)
@@ -602,6 +617,21 @@ __global__ void __launch_bounds__(256) k_convlstm_fwd_frames(RecFwdParams<GT> p)
       barrier_lds();
       if (tid == 0)
         __hip_atomic_store(p.flags + b * kRecBands + band, t + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else if constexpr (RST) {
+      const bool rn = t + 1 < p.T && p.reset[(size_t)(t + 1) * p.B + b] != 0.f;   // frame b enters step t+1 from reset()
+      for (int i = tid; i < P * HC; i += 256) {   // (each thread zeroes only the image chunks it has just read)
+        const int px = i / HC, q = i % HC;
+        u32x4* im = reinterpret_cast<u32x4*>(himb + pixb(hidx(px)) + q * 16);
+        const u32x4 v = *im;
+        *reinterpret_cast<u32x4*>(p.HR + (rowt + px) * 128 + q * 8) = v;
+        *reinterpret_cast<u32x4*>(p.XH + (rown + px) * 192 + 64 + q * 8) = rn ? u32x4{0u, 0u, 0u, 0u} : v;
+        if (rn) *im = u32x4{0u, 0u, 0u, 0u};
+      }
+      if (rn) {
+#pragma unroll
+        for (int k = 0; k < NRB * 16; ++k) cw[k * 64] = 0.f;
+        barrier_lds();   // the next step's x-part ends with the h-part's first fragment reads of the image
+      }
     } else if constexpr (G == 1) {
       for (int i = tid; i < ((ABL & 2) ? 0 : P * HC); i += 256) {
         const int px = i / HC, q = i % HC;
@@ -648,7 +678,7 @@ inline hipError_t convlstm_fwd_frames(const RecFwdParams<GT>& p, int G, hipStrea
   RecFwdParams<GT> q = p;
   rec_columns(p.h, p.w, q.colpp, q.colhb);
   if (G == 2) {
-    if (!p.flags || !p.report || p.spin < 0) return hipErrorInvalidValue;
+    if (!p.flags || !p.report || p.spin < 0 || p.reset) return hipErrorInvalidValue;   // (no mask form of the pair)
     const void* k = reinterpret_cast<const void*>(&k_convlstm_fwd_frames<GT, 2, 0>);
 #ifdef AAA_ABLATION   // diagnostic builds only (tools/ubench): the product library never reads AAA_REC_ABL
     const char* e = getenv("AAA_REC_ABL");
@@ -666,6 +696,11 @@ inline hipError_t convlstm_fwd_frames(const RecFwdParams<GT>& p, int G, hipStrea
     default: break;
   }
 #endif
+  if (p.reset) {   // the mask variant (G = 1 above: a mask with G = 2 was refused)
+    if (!p.HR) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((k_convlstm_fwd_frames<GT, 1, 0, false, true>), dim3(p.B), dim3(256), 0, st, q);
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL((k_convlstm_fwd_frames<GT, 1, 0>), dim3(p.B), dim3(256), 0, st, q);
   return hipGetLastError();
 }

@@ -90,6 +90,7 @@ struct RecBwdParams {   // dO, Gt, Cst: per-(frame, step) slices, channel-quad-m
   int rowpad = 0;         // single-workgroup kernel: 16-B slots after each image row (0 or 14: bw_rowpad)
   int sc1_all = 0;        // band kernel: every dZ store / chunk piece sc1 (A/B), not only the exchanged rows
   int ring = 0;           // single-workgroup kernel: the LDS-DMA epilogue ring (k_convlstm_bwd_frames RING)
+  const float* reset = nullptr;   // single-workgroup kernel's RST variant: the (T, B) episode-start mask
 };
 
 // Chunk images of the band kernel: image pixel ip (a (rows+2) x (w+2)
@@ -149,9 +150,20 @@ __device__ uint64_t aaa_bw_stamps[1024 * 64 * 8];
 // vmcnt) the compiler treats the counter as out of order and waits vmcnt(0) before every unit, so the
 // register ring never had more than one unit in flight; the DMA'd ring keeps kBwEpD units in flight.
 constexpr int kBwEpD = 4;   // RING: unit slots per wave (4 pieces of 1 KB each: c_{s-1}, gates 0-7, gates 8-15, dc)
-template <int ABL = 0, bool BAND = false, bool DOACC = !BAND, bool RING = false>
+//
+// RST (single-workgroup kernel, no ring: one workgroup owns the frame): episode starts, p.reset[t][b] != 0 = frame b
+// entered step t from the reset() state.  The mask is frame-uniform, so every branch on it is workgroup-uniform, and
+// it only selects in the gate backward of step s (the case analysis of recur_bwd_f32.h's RST variant):
+//   reset[s+1][b]: nothing flows in from step s+1 -- dh_s = dO_s alone (the accumulators, dO_s + W^T dZ_{s+1}, are
+//                  not read: dO_s is loaded again) and the dc carry in is 0;
+//   reset[s][b]:   c_{s-1} is read as 0 (so c_s = i c~, as the forward computed it) and d f-gate = 0;
+//   reset[0][b]:   dh0 and the dc carry out are written as 0.
+// The GEMMs, the dx rows, the bias partials and the dZ stores are what they are without a mask; at steps without a
+// reset the arithmetic is the plain kernel's, operation for operation.
+template <int ABL = 0, bool BAND = false, bool DOACC = !BAND, bool RING = false, bool RST = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) k_convlstm_bwd_frames(RecBwdParams p) {
   static_assert(!RING || (!BAND && DOACC), "the DMA'd epilogue ring is the single-workgroup DOACC kernel's");
+  static_assert(!RST || (!BAND && !RING && ABL == 0), "the mask form exists only where one workgroup owns a frame");
   constexpr bool SWZ = BAND;             // swizzled 256-B pixel rows (band) or 272-B rows
   constexpr int PIT = SWZ ? 256 : 272;   // image pixel pitch (bytes)
   constexpr int IMG = SWZ ? kBwIBS : kBwIBP;   // bytes per chunk image
@@ -374,6 +386,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     const __amdgpu_buffer_rsrc_t rz = make_rsrc(p.dZ + rows * 512, (uint32_t)(P * 512 * 2));
     const __amdgpu_buffer_rsrc_t rdc = make_rsrc(p.dC + (size_t)b * P * 128, (uint32_t)(P * 128 * 4));   // RING
     (void)rdc;
+    bool rin = false, rc = false;   // RST: the frame entered step s+1 / step s from reset()
+    if constexpr (RST) {
+      rin = !first && p.reset[(size_t)(s + 1) * p.B + b] != 0.f;
+      rc = p.reset[(size_t)s * p.B + b] != 0.f;
+    }
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       float bs[16];   // [e][gate] sums over the lane's pixels (this channel group)
@@ -432,6 +449,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         if (col < Pb) {
           const int pp = pix0 + col;
           f32x4 dh{acc[cb][4 * g], acc[cb][4 * g + 1], acc[cb][4 * g + 2], acc[cb][4 * g + 3]};
+          if constexpr (RST) {
+            if (rin) {   // dh_s = dO_s alone
+              if constexpr (DOACC)
+                dh = *reinterpret_cast<const f32x4*>(p.dO + rows * 128 + slc4(pp, ch, P, p.cqm & kCqmDO));
+              else
+                dh = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+          }
           if constexpr (!DOACC) {
             dh[0] += in.dO[0]; dh[1] += in.dO[1]; dh[2] += in.dO[2]; dh[3] += in.dO[3];
             if (first && p.dhT) {
@@ -441,6 +466,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
           }
           f32x4* dcp = dcl + wave * 16 * 64 + ln + (g * 4 + cb) * 64;
           f32x4 dc = *dcp;
+          f32x4 cpv = in.cp;
+          if constexpr (RST) {
+            if (rin) dc = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (rc) cpv = f32x4{0.f, 0.f, 0.f, 0.f};
+          }
           float dz[16];
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
@@ -449,7 +479,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
             const h2 a = __builtin_bit_cast(h2, w01), c2 = __builtin_bit_cast(h2, w23);
             const f32x4 gv{(float)a[0], (float)a[1], (float)c2[0], (float)c2[1]};
             float d = dc[e], di, df, dcg, dout;
-            gate_bwd_fast(dh[e], gv, in.cp[e], gv[1] * in.cp[e] + gv[0] * gv[2], d, di, df, dcg, dout);
+            gate_bwd_fast(dh[e], gv, cpv[e], gv[1] * cpv[e] + gv[0] * gv[2], d, di, df, dcg, dout);
+            if constexpr (RST) {
+              if (rc) df = 0.f;
+            }
             dc[e] = d;
             dz[4 * e] = di; dz[4 * e + 1] = df; dz[4 * e + 2] = dcg; dz[4 * e + 3] = dout;
             bs[4 * e] += di; bs[4 * e + 1] += df; bs[4 * e + 2] += dcg; bs[4 * e + 3] += dout;
@@ -713,6 +746,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     if (t > 0) {
       epilogue(t - 1, acc, ring, false);
     } else if (p.dh0) {   // dh_{-1}: the gradient of the initial state h0
+      bool r0s = false;   // RST: the frame started an episode at step 0 -- h0 was not read
+      if constexpr (RST) r0s = p.reset[b] != 0.f;
 #pragma unroll
       for (int cb = 0; cb < 4; ++cb) {
         const int col = cb * 32 + r32;
@@ -720,7 +755,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
 #pragma unroll
           for (int g = 0; g < 4; ++g)
             *reinterpret_cast<f32x4*>(p.dh0 + ((size_t)b * P + pix0 + col) * 128 + 32 * wave + 8 * g + 4 * hh) =
-                f32x4{acc[cb][4 * g], acc[cb][4 * g + 1], acc[cb][4 * g + 2], acc[cb][4 * g + 3]};
+                RST && r0s ? f32x4{0.f, 0.f, 0.f, 0.f}
+                           : f32x4{acc[cb][4 * g], acc[cb][4 * g + 1], acc[cb][4 * g + 2], acc[cb][4 * g + 3]};
       }
     }
     barrier_lds();   // chunk images 0, 1 of dZ_{t-1} complete
@@ -753,6 +789,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
   }
   // dc carry out (dc_0; RING: already in p.dC, written by the last epilogue)
   if constexpr (!RING) {
+    bool r0s = false;   // RST: c0 was not read either
+    if constexpr (RST) r0s = p.reset[b] != 0.f;
 #pragma unroll
     for (int g = 0; g < 4; ++g)
 #pragma unroll
@@ -760,7 +798,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         const int col = cb * 32 + r32;
         if (col < Pb)
           *reinterpret_cast<f32x4*>(p.dC + ((size_t)b * P + pix0 + col) * 128 + 32 * wave + 8 * g + 4 * hh) =
-              dcw[(g * 4 + cb) * 64];
+              RST && r0s ? f32x4{0.f, 0.f, 0.f, 0.f} : dcw[(g * 4 + cb) * 64];
       }
   }
 }
@@ -1109,6 +1147,7 @@ inline hipError_t convlstm_bwd_pairs(const RecBwdParams& p, hipStream_t st) {
   if (!rec_fits(p.h, p.w) || p.P != p.h * p.w || p.B < 1 || p.T < 1 || !p.flags || !p.report || p.spin < 0 ||
       (p.rowpad && p.rowpad != bw_rowpad(p.h, p.w)))
     return hipErrorInvalidValue;
+  if (p.reset) return hipErrorInvalidValue;   // no mask form of the pair
   RecBwdParams q = p;
   return launch_resident(reinterpret_cast<const void*>(&k_convlstm_bwd_pairs<0>), 2 * p.B, 256, q, st);
 }
@@ -1133,6 +1172,11 @@ inline hipError_t convlstm_bwd_frames(const RecBwdParams& p, hipStream_t st) {
     return hipGetLastError();
   }
 #endif
+  if (p.reset) {   // the mask variant: the plain kernel's arithmetic (DOACC) with the selects of RST
+    if (p.ring) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((k_convlstm_bwd_frames<0, false, true, false, true>), dim3(p.B), dim3(256), 0, st, p);
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL((k_convlstm_bwd_frames<0>), dim3(p.B), dim3(256), 0, st, p);
   return hipGetLastError();
 }
@@ -1144,6 +1188,7 @@ inline bool bw_band_fits(int h, int w) { return rec_band_fits(h, w) && kRecNPHB 
 inline hipError_t convlstm_bwd_band(const RecBwdParams& p, hipStream_t st) {
   if (!bw_band_fits(p.h, p.w) || p.P != p.h * p.w || p.B < 1 || p.T < 1 || !p.flags || !p.report || p.spin < 0)
     return hipErrorInvalidValue;
+  if (p.reset) return hipErrorInvalidValue;   // no mask form of the band kernel
   RecBwdParams q = p;
   const void* k = reinterpret_cast<const void*>(&k_convlstm_bwd_frames<0, true>);
 #ifdef AAA_ABLATION   // diagnostic builds only

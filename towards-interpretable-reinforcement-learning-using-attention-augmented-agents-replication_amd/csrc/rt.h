@@ -72,12 +72,13 @@ struct Layout {
   int B, T, F, H, W, H1, W1, P1, h, w, P, nq, A, dt, esz;
   int sc;   // stateful policy core (AAA_FLAG_STATEFUL_CORE)
   int fu8;  // frames are uint8 (AAA_FLAG_FRAMES_U8)
+  int br;   // bf16 cfg that takes episode-start masks (AAA_FLAG_BF16_RESETS): the HR region exists
   int fchunk;   // frames per launch of the whole-batch conv GEMMs (< 2 GiB per descriptor, check_ranges)
   int xpc;      // frames of the Xp chunk buffer (conv1's bordered RGBx operand, rebuilt per chunk)
   int qd, da, ans_in, ans_ld, ldy;
   size_t poff[NPARAM], psz[NPARAM], ptotal;
   size_t k_Wp1, k_Wp2, k_WdT2, k_W1s, k_W2s, k_WpX, k_WpH, k_WpXH, k_Wfr, k_Wbf, k_Wf32, k_Wb32, k_Wf6, k_Wf6p, k_Wb6, k_Wx6, k_Wb6p, k_Wx6p, k_WdTl, k_WdTc, k_WdT6, k_bl, k_Wihhp, k_q1, k_q2, k_Q, k_W1p, k_Wihp, k_blc, k_Whd, k_bhd, k_WdT2s, packed;
-  size_t Xp, Y1, XH, Hs, Cst, Gt, SQ, Am, ans, hid1, AO, LG, LC, LH;
+  size_t Xp, Y1, XH, Hs, HR, Cst, Gt, SQ, Am, ans, hid1, AO, LG, LC, LH;
   size_t dY, dLG, dAO, dH1, dAns, dO, dQp, dQs, dC, dZ, dZp, dY2, dY1, dxb, rflags, xpart, dhs, dZ6;
   size_t gWp1, gWp2, gWpl, gbl, gW1p, gWihp, gblc, gWhd, gbhd, ws;
   // stateful core: state slots, per-step query activations, [answer | h] rows, their grads
@@ -255,7 +256,8 @@ struct RecurPlan {
   bool fb32;                // fp32 frame-group BPTT (G = 8)
   int cqm;                  // recur.h kCqm* mask of the channel-quad-major Cst / Gt / dO slices; 0: all row-major
 };
-// resets: the call carries an episode-start mask (fp32), which not every frame-group kernel takes
+// resets: the call carries an episode-start mask, which not every frame kernel takes (bf16: none of the paired,
+// band-mode and BPTT frame kernels)
 RecurPlan recur_plan(const Layout& L, bool resets);
 bool gates_f16(int dt, int M);   // the plan's g16 for the component cell entries, which have no Layout
 
@@ -555,7 +557,10 @@ int device_cus();   // CUs of the current device (which frame kernel runs, and t
 // is kept -- the readout reads the bf16 h the next step's conv and the weight
 // gradient read, oracle/ref_cpu.py h_store).  Frame f = t*B + b sits at
 // .frame(f, P) either way.
-inline OSrc readout_h(const Layout& L, char* ws) {
+// Under an episode-start mask (bf16, AAA_FLAG_BF16_RESETS) XH's h half holds zeros in the rows that start an
+// episode, so the masked forward keeps every h_t in HR as well and the readout of a masked call reads it there.
+inline OSrc readout_h(const Layout& L, char* ws, bool masked) {
+  if (L.esz == 2 && masked) return o_bf16((const __bf16*)(ws + L.HR), 128);
   if (L.esz == 2) return o_bf16((const __bf16*)(ws + L.XH) + (size_t)L.B * L.P * 192 + 64, 192);
   return o_f32((const float*)(ws + L.Hs));
 }
@@ -588,7 +593,7 @@ template <typename T, typename OT>
 int vision_fwd(const Layout& L, int F, const char* pk, const float* prm, const void* frames, T* Xp, T* Y1, OT* out,
                int out_ld, hipStream_t st, bool xp_full = true, std::string* ran = nullptr,   // ran <- the kernels taken
                bool resident_xp = true);   // false: a frame-resident kernel stores no Xp (the learner; ran says "no Xp")
-// reset: the episode-start mask (T, B) of aaa_forward_resets / aaa_backward_resets (fp32 only), or null
+// reset: the episode-start mask (T, B) of aaa_forward_resets / aaa_backward_resets, or null
 template <typename T>
 int forward_impl(const Layout& L, const aaa_io* io, hipStream_t st, int phases, const float* reset = nullptr);
 template <typename T>

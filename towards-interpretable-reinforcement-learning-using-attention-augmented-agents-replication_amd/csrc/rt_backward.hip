@@ -603,7 +603,7 @@ static int head_backward_stateful(const CallCtx& c) {
     // the logits path plus the answer row's copy of Q
     {
       TimerScope tim(AAA_TIMER_ATTN_BWD, st, (double)B * attn_bwd_bytes(P, L.nq, L.esz), "k_attn_bwd, per-frame query (stateful core)");
-      HIPCHK(attn_bwd(readout_h(L, c.ws).frame(f0, P), io->basis, c.Wf(L.Qf) + f0 * qd, c.Wf(L.Am) + f0 * P * L.nq, dAns,
+      HIPCHK(attn_bwd(readout_h(L, c.ws, c.reset != nullptr).frame(f0, P), io->basis, c.Wf(L.Qf) + f0 * qd, c.Wf(L.Am) + f0 * P * L.nq, dAns,
                       da, B, P, L.nq, c.Wf(L.dO) + f0 * P * 128, dQf, st, qd, 1, (c.plan.cqm & kCqmDO) != 0));
     }
     // query MLP backward to its input h_{t-1}
@@ -686,7 +686,7 @@ static int head_backward_zero_state(const CallCtx& c) {
   // attention readout / softmax / logits backward, then the query MLP
   {
     TimerScope tim(AAA_TIMER_ATTN_BWD, st, (double)F * attn_bwd_bytes(P, L.nq, L.esz), "k_attn_bwd, 1 WG per frame");
-    HIPCHK(attn_bwd(readout_h(L, c.ws), c.io->basis, (const float*)(c.pk + L.k_Q), c.Wf(L.Am), c.Wf(L.dAns), L.da, F, P,
+    HIPCHK(attn_bwd(readout_h(L, c.ws, c.reset != nullptr), c.io->basis, (const float*)(c.pk + L.k_Q), c.Wf(L.Am), c.Wf(L.dAns), L.da, F, P,
                     L.nq, c.Wf(L.dO), c.Wf(L.dQp), st, 0, 0, (c.plan.cqm & kCqmDO) != 0));
   }
   tail.reset(new TimerScope(AAA_TIMER_TAIL_BWD, st, 0.0, "bias column sums, query MLP backward, grad unpack"));
@@ -715,7 +715,7 @@ static int head_backward(const CallCtx& c) {
     TimerScope tim(AAA_TIMER_MISC, c.st, 0.0, "grad/accumulator memsets, cotangent concat");
     ZeroRanges z{};   // the grads, the atomic accumulators and the cotangent concat: one launch
     z.add(c.grads, (long)L.ptotal);
-    z.add(c.Wf(L.dQs), (long)((L.ws - L.dQs) / 4));
+    z.add(c.Wf(L.dQs), (long)((L.HR - L.dQs) / 4));   // (up to HR, the last region: not an accumulator)
     HIPCHK(prologue<T>(z, 0, nullptr, (T*)nullptr, L.F, L.A, L.ldy, c.io->dlogits, c.io->dvalues, c.Wf(L.dY), c.st));
   }
   return L.sc ? head_backward_stateful(c) : head_backward_zero_state(c);
@@ -887,23 +887,46 @@ struct BpttChain {
   float* part;   // gate-bias partials [T][cdiv(M, bj)][512], or null: the bias is dZ's column sum
 };
 
-// Episode starts (reset != null, fp32): the step kernels run as they are, then resets.hip's
+// Episode starts (reset != null), fp32: the step kernels run as they are, then resets.hip's
 // k_reset_gate_bwd rewrites the rows of step t-1's gate backward that an episode start at t or
 // t-1 changes.  Called after the gate backward of step t-1 (t = T: the last step's).
+// bf16 runs the whole gate backward of a masked call in resets.hip instead (bptt_gates_resets).
 template <typename T>
 static int bptt_fix(const CallCtx& c, int t) {
   if (!c.reset) return AAA_OK;
   if constexpr (std::is_same<T, float>::value) {
     const Layout& L = c.L;
     const int M = L.B * L.P;
-    HIPCHK(reset_gate_bwd(t < L.T ? c.reset + (size_t)t * L.B : nullptr, c.reset + (size_t)(t - 1) * L.B, M, L.P,
-                          c.Wf(L.dO) + (size_t)(t - 1) * M * 128, c.Wf(L.Gt) + (size_t)(t - 1) * M * 512,
-                          c.Wf(L.Cst) + (size_t)(t - 1) * M * 128, c.Wf(L.Cst) + (size_t)t * M * 128, c.Wf(L.dC),
-                          c.Wf(L.dZ) + (size_t)(t - 1) * M * 512, c.st));
-    return AAA_OK;
-  } else {
-    return fail(AAA_E_ARG, "episode-start masks: fp32 only");
+    HIPCHK((reset_gate_bwd(t < L.T ? c.reset + (size_t)t * L.B : nullptr, c.reset + (size_t)(t - 1) * L.B, M,
+                                         L.P, c.Wf(L.dO) + (size_t)(t - 1) * M * 128,
+                                         c.Wf(L.Gt) + (size_t)(t - 1) * M * 512, c.Wf(L.Cst) + (size_t)(t - 1) * M * 128,
+                                         c.Wf(L.Cst) + (size_t)t * M * 128, c.Wf(L.dC),
+                                         c.Wf(L.dZ) + (size_t)(t - 1) * M * 512, c.st)));
   }
+  return AAA_OK;
+}
+
+// bf16 under a mask: the gate backward of step t-1 (t = T: the last step's) with the mask applied, from the raw
+// dgrad ``dh`` of dZ_t (t = T: io->dhT or null), its fp32 gate-bias partials into ch.part (resets.hip
+// k_gate_bwd_resets).  The rounded dZ never feeds the bias gradient, as without a mask.
+static int bptt_gates_resets(const CallCtx& c, const BpttChain& ch, int t, const float* dh) {
+  const Layout& L = c.L;
+  const int M = L.B * L.P;
+  const float* rs_in = t < L.T ? c.reset + (size_t)t * L.B : nullptr;
+  const float* rs_c = c.reset + (size_t)(t - 1) * L.B;
+  const float* dO = c.Wf(L.dO) + (size_t)(t - 1) * M * 128;
+  const float* cprev = c.Wf(L.Cst) + (size_t)(t - 1) * M * 128;
+  const float* ccur = c.Wf(L.Cst) + (size_t)t * M * 128;
+  __bf16* dz = c.Wt<__bf16>(L.dZ) + (size_t)(t - 1) * M * 512;
+  float* part = ch.part ? ch.part + (size_t)(t - 1) * cdiv(M, ch.bj) * 512 : nullptr;
+  if (ch.g16)
+    HIPCHK((gate_bwd_resets<__bf16, _Float16>(M, ch.bj, L.P, rs_in, rs_c, dO, dh,
+                                              (const _Float16*)(c.ws + L.Gt) + (size_t)(t - 1) * M * 512, cprev, ccur,
+                                              c.Wf(L.dC), dz, part, c.st)));
+  else
+    HIPCHK((gate_bwd_resets<__bf16, float>(M, ch.bj, L.P, rs_in, rs_c, dO, dh, c.Wf(L.Gt) + (size_t)(t - 1) * M * 512,
+                                           cprev, ccur, c.Wf(L.dC), dz, part, c.st)));
+  return AAA_OK;
 }
 
 // The gate backward of the last step (dh_T from io->dhT), which starts the per-step and frame-group chains
@@ -911,6 +934,8 @@ template <typename T>
 static int bptt_last_gates(const CallCtx& c, const BpttChain& ch) {
   const Layout& L = c.L;
   const int M = L.B * L.P, t1 = L.T - 1;
+  if constexpr (std::is_same<T, __bf16>::value)
+    if (c.reset) return bptt_gates_resets(c, ch, L.T, c.io->dhT);
   float* part = ch.part ? ch.part + (size_t)t1 * cdiv(M, ch.bj) * 512 : nullptr;
   if (ch.g16)
     HIPCHK((gate_bwd_last<T, _Float16>(M, ch.bj, c.Wf(L.dO) + (size_t)t1 * M * 128, c.io->dhT,
@@ -941,6 +966,11 @@ static int bptt_frames_bf16(const CallCtx& c, int fb) {
   rp.sc1_all = ab_int("AAA_BW_SC1_ALL", 0);   // band kernel (A/B): sc1 for every dZ row, as in round 4
   // single-workgroup kernel: the epilogue's inputs by LDS-DMA into a counted ring (recur_bwd.h RING)
   rp.ring = fb == 1 && ab_int("AAA_BW_RING", 0);   // measured slower: ablation builds only
+  if (c.reset) {   // the single-workgroup kernel's mask variant (recur_bwd.h RST; the plan sends no other here)
+    if (fb != 1) return fail(AAA_E_LAUNCH, "episode-start masks: no paired or band-mode bf16 BPTT kernel takes one");
+    rp.reset = c.reset;
+    rp.ring = 0;
+  }
   if (fb >= 2)   // paired or band mode: hand-off flags [B][fb]
     if (const int rc = report_word("paired-kernel", &rp.report)) return rc;
   {
@@ -950,7 +980,7 @@ static int bptt_frames_bf16(const CallCtx& c, int fb) {
                        ? strf("bf16 band-mode frame-resident BPTT + dx, %d steps per launch, %d bands per frame, "
                               "fp16 gates [kernel: k_convlstm_bwd_frames<0, true]", L.T, fb)
                        : strf("bf16 frame-resident BPTT + dx, %d steps per launch, %d WG per frame, fp16 gates "
-                              "[kernel: %s]", L.T, fb, fb == 2 ? "k_convlstm_bwd_pairs" : (rp.ring ? "k_convlstm_bwd_frames<ring>" : "k_convlstm_bwd_frames<0, false")));
+                              "[kernel: %s]%s", L.T, fb, fb == 2 ? "k_convlstm_bwd_pairs" : (rp.ring ? "k_convlstm_bwd_frames<ring>" : "k_convlstm_bwd_frames<0, false"), c.reset ? ", resets" : ""));
     HIPCHK(fb == 2 ? convlstm_bwd_pairs(rp, c.st) : (fb == 1 ? convlstm_bwd_frames(rp, c.st) : convlstm_bwd_band(rp, c.st)));
   }
   HIPCHK(colsum<float>(c.Wf(L.dxb), 64, L.B, 64, c.grads + L.poff[C1B], c.st));
@@ -999,14 +1029,18 @@ template <typename T>
 static int bptt_step(const CallCtx& c, const BpttChain& ch, int t) {
   const Layout& L = c.L;
   const int M = L.B * L.P, ntj = cdiv(M, ch.bj);
-  const bool prev = t > 0;
+  // bf16 under a mask: the GEMM stores the raw dgrad (its t = 0 form) into dO slot t -- dO_t was consumed by the gate
+  // backward of step t, the launch before this one -- and the gate backward of step t-1 follows as a launch of its own
+  const bool rawdh = c.reset && std::is_same<T, __bf16>::value && t > 0;
+  const bool prev = t > 0 && !rawdh;
   const ConvGeo g = ConvGeo{512, 512, 0, L.h, L.w, L.h, L.w, 3, 1, 1, 1}.prep();
   const T* dzt = c.Wt<T>(L.dZ) + (size_t)t * M * 512;
   const uint32_t dz_bytes = (uint32_t)((size_t)M * 512 * L.esz);  // one step slice of dZ
   const T* WdTh = (const T*)(c.pk + L.k_WdTl) + (size_t)64 * 4608;
   float* part = ch.part && prev ? ch.part + (size_t)(t - 1) * ntj * 512 : nullptr;
-  TimerScope tim(AAA_TIMER_BPTT_STEP, c.st, 2.0 * M * 128 * 4608, strf("%s dh dgrad + fused gate bwd, K=4608, AAA_BPTT_TILE %d%s%s", std::is_same<T, float>::value ? "fp32" : "bf16", ch.tile, ch.g16 ? ", fp16 gates [kernel: EpiConvLstmBwd]" : " [kernel: EpiConvLstmBwd]", c.reset ? ", resets" : ""));
-  const int tile_id = prev ? ch.tile : ch.dh0;
+  TimerScope tim(AAA_TIMER_BPTT_STEP, c.st, 2.0 * M * 128 * 4608, strf("%s dh dgrad + %s gate bwd, K=4608, AAA_BPTT_TILE %d%s%s", std::is_same<T, float>::value ? "fp32" : "bf16", rawdh ? "masked (k_gate_bwd_resets)" : "fused", ch.tile, ch.g16 ? ", fp16 gates [kernel: EpiConvLstmBwd]" : " [kernel: EpiConvLstmBwd]", c.reset ? ", resets" : ""));
+  // (the raw-dh form of a masked bf16 step: the plan's tile, as the fused form; a split-K family's through its t = 0 entry)
+  const int tile_id = prev || (rawdh && ch.split == SplitK::None) ? ch.tile : ch.dh0;
   auto step = [&](auto gtag) -> int {
     using GT = decltype(gtag);
     using EB = EpiConvLstmBwd<T, GT>;
@@ -1015,7 +1049,7 @@ static int bptt_step(const CallCtx& c, const BpttChain& ch, int t) {
     float* dO = prev ? c.Wf(L.dO) + (size_t)(t - 1) * M * 128 : nullptr;
     T* dzp = prev ? c.Wt<T>(L.dZ) + (size_t)(t - 1) * M * 512 : nullptr;
     const EB ep{nullptr, gates, cprev, c.Wf(L.Cst) + (size_t)t * M * 128, dO, c.Wf(L.dC), dzp,
-                prev ? nullptr : c.io->dh0, prev ? 1 : 0, M, 64, part};
+                prev ? nullptr : (rawdh ? c.Wf(L.dO) + (size_t)t * M * 128 : c.io->dh0), prev ? 1 : 0, M, 64, part};
     return for_tile<BpttTiles>(tile_id, (int)AAA_E_ARG, [&](auto tile) -> int {
       using Tl = decltype(tile);
       using CK = typename Tl::template Cfg<T>;
@@ -1044,6 +1078,7 @@ static int bptt_step(const CallCtx& c, const BpttChain& ch, int t) {
     });
   };
   if (const int rc = ch.g16 ? step(_Float16{}) : step(float{})) return rc;
+  if (rawdh) return bptt_gates_resets(c, ch, t, c.Wf(L.dO) + (size_t)t * M * 128);
   return prev ? bptt_fix<T>(c, t) : AAA_OK;
 }
 
@@ -1085,9 +1120,10 @@ static int core_backward(const CallCtx& c, int phases, LstmGrads* deferred_unpac
   const int fb = c.plan.fb;   // bf16: workgroups per frame of the frame-resident launch, 0: none
   const bool fb32 = c.plan.fb32;   // fp32: the frame-group launch (a mask: its RST variant, with dx fused)
   // Gate-bias partials from the step kernels' epilogues: ring tiles only; not where the frame-group kernel
-  // writes its own per-(step, frame) partials (step T-1's included); not under a mask, where the gate-bias
-  // gradient is the column sum of the final dZ, not of partials taken before bptt_fix's rewrite.
-  ch.part = ch.pipe && !fixk && !fb32 && !c.reset ? c.Wf(L.dZp) : nullptr;
+  // writes its own per-(step, frame) partials (step T-1's included); not under an fp32 mask, where the gate-bias
+  // gradient is the column sum of the final (fp32) dZ, not of partials taken before bptt_fix's rewrite.  (bf16
+  // under a mask: the masked gate backward writes the partials itself, bptt_gates_resets.)
+  ch.part = ch.pipe && !fixk && !fb32 && !(c.reset && std::is_same<T, float>::value) ? c.Wf(L.dZp) : nullptr;
   if (!fb)
     if (const int rc = bptt_last_gates<T>(c, ch)) return rc;
   misc.reset();

@@ -27,9 +27,10 @@ int build_layout(const aaa_cfg* c, Layout& L, int min_frames) {
   if (c->nq != 4 && c->nq != 8) return fail(AAA_E_ARG, "nq must be 4 or 8 (got %d)", c->nq);
   if (c->A < 1 || c->A > 256) return fail(AAA_E_ARG, "A out of range (%d)", c->A);
   if (c->dtype != AAA_F32 && c->dtype != AAA_BF16) return fail(AAA_E_ARG, "bad dtype %d", c->dtype);
-  if (c->flags & ~(AAA_FLAG_STATEFUL_CORE | AAA_FLAG_FRAMES_U8 | AAA_FLAG_DEFER_STRANDED)) return fail(AAA_E_ARG, "unknown flags 0x%x", c->flags);
+  if (c->flags & ~(AAA_FLAG_STATEFUL_CORE | AAA_FLAG_FRAMES_U8 | AAA_FLAG_DEFER_STRANDED | AAA_FLAG_BF16_RESETS)) return fail(AAA_E_ARG, "unknown flags 0x%x", c->flags);
   L.sc = (c->flags & AAA_FLAG_STATEFUL_CORE) != 0;
   L.fu8 = (c->flags & AAA_FLAG_FRAMES_U8) != 0;
+  L.br = c->dtype == AAA_BF16 && (c->flags & AAA_FLAG_BF16_RESETS) != 0;
   L.B = c->B; L.T = c->T; L.F = c->B * c->T; L.H = c->H; L.W = c->W;
   L.H1 = conv_out(c->H, 8, 4, 1); L.W1 = conv_out(c->W, 8, 4, 1);
   L.h = conv_out(L.H1, 4, 2, 2); L.w = conv_out(L.W1, 4, 2, 2);
@@ -164,6 +165,9 @@ int build_layout(const aaa_cfg* c, Layout& L, int min_frames) {
   L.gWhd = take((size_t)L.ldy * 256 * 4);
   L.gbhd = take((size_t)L.ldy * 4);
   L.gWihhp = take(L.sc ? 1024 * 512 * 4 : 0);
+  // AAA_FLAG_BF16_RESETS: h_t for the readout of a masked call (rt.h readout_h), behind everything else so that
+  // every other offset is the unflagged cfg's
+  L.HR = take(L.br ? F * P * 128 * 2 : 0);
   L.ws = p;
   return check_ranges(L, min_frames > 0 ? min_frames : L.B);
 }
@@ -496,18 +500,26 @@ RecurPlan recur_plan(const Layout& L, bool resets) {
   p.gate_bytes = p.g16 ? 2 : 4;
   // The forward's path.  fp32: the frame-group launch, under a mask only where its RST variant exists (recur_f32.h
   // f32_fwd_resets).  Then, with the fused x-part, bf16's band mode or frame-resident launch; else step by step.
+  // bf16 under a mask (AAA_FLAG_BF16_RESETS): only the paths that have a mask form -- the single-workgroup
+  // frame-resident forward (recur.h RST) where the forward's rule gives G = 1 and, behind it, the single-workgroup
+  // frame-resident BPTT (recur_bwd.h RST) where AAA_FRAMES_BWD's rule gives 1; else the per-step kernels.  Paired
+  // and band kernels never run under a mask.
+  const bool brst = resets && L.dt == AAA_BF16;
   const int G32 = f32_frames(L);
   if (G32 && !(resets && !f32_fwd_resets(f32_split6(), G32, L.P))) p.fwd = RecurFwd::FramesF32, p.fwd_g = G32;
   else if (!p.fused_x) p.fwd = RecurFwd::XpartSteps;
-  else if (const int nb = frames_band(L)) p.fwd = RecurFwd::BandBf16, p.fwd_g = nb;
-  else if (const int G = frames_g(L, "AAA_FRAMES_FWD")) p.fwd = RecurFwd::FramesBf16, p.fwd_g = G;
+  else if (const int nb = brst ? 0 : frames_band(L)) p.fwd = RecurFwd::BandBf16, p.fwd_g = nb;
+  else if (const int G = frames_g(L, "AAA_FRAMES_FWD"); brst ? G == 1 : G != 0) p.fwd = RecurFwd::FramesBf16, p.fwd_g = G;
   else p.fwd = RecurFwd::FusedSteps;
   // The BPTT chain on the frame-resident kernels (recur_bwd.h; fp16 gate storage), only behind a frame-resident
   // forward: band mode wherever the forward runs in band mode, else workgroups per frame as the forward's rule
   // (AAA_FRAMES_BWD = 0 / 1 / 2 forces it).  The two share the channel-quad-major slices of Cst / Gt / dO
   // (recur.h cqm4), which the per-step kernels do not read.
   if (p.g16 && p.fwd == RecurFwd::BandBf16) p.fb = bw_band_fits(L.h, L.w) ? p.fwd_g : 0;
-  else if (p.g16 && p.fwd == RecurFwd::FramesBf16) p.fb = frames_g(L, "AAA_FRAMES_BWD");
+  else if (p.g16 && p.fwd == RecurFwd::FramesBf16) {
+    p.fb = frames_g(L, "AAA_FRAMES_BWD");
+    if (brst && p.fb != 1) p.fb = 0;
+  }
   // fp32: the frame-group BPTT behind the forward's G = 8 (a mask: its RST variant, the split-product kernel)
   p.fb32 = L.dt == AAA_F32 && (!resets || f32_split6()) && G32 == 8 && env_int("AAA_F32_FRAMES_BWD", 1);
   static const int mask = ab_int("AAA_CQM", kCqmC | kCqmG | kCqmDO) & 7;   // A/B: tools/gpu_ab.sh

@@ -226,18 +226,34 @@ static int state_in(const CallCtx& c, bool core) {
 static float* hs_out(const CallCtx& c, int t) {
   return c.L.esz == 4 ? c.Wf(c.L.Hs) + (size_t)t * (c.L.B * c.L.P) * 128 : (float*)nullptr;
 }
-// Episode starts (reset != null, fp32): before step t, zeros in the h half of XH slot t for the rows
+// Episode starts (reset != null): before step t, zeros in the h half of XH slot t for the rows
 // that enter it from reset() and a masked copy of c_{t-1} (in dC: the BPTT's carry, idle in the
 // forward) -- Cst slot t keeps the true c_{t-1}, which step t-1's own backward reads (resets.hip).
+// bf16: slot t's h half is also the only copy of h_{t-1}, so it goes to HR slot t-1 (the readout's
+// copy, rt.h readout_h) before the rows are zeroed.
 // *cp <- the c_{t-1} the step's cell update reads.
+template <typename T>
 static int c_in(const CallCtx& c, int t, const float** cp) {
   const Layout& L = c.L;
   const int M = L.B * L.P;
   *cp = c.Wf(L.Cst) + (size_t)t * M * 128;
   if (!c.reset) return AAA_OK;
-  HIPCHK(reset_rows(c.reset + (size_t)t * L.B, L.B, L.P,
-                    ResetZeros{}.add(c.Wf(L.XH) + (size_t)t * M * 192 + 64, 192, 128), *cp, c.Wf(L.dC), 128, c.st));
+  T* xht = c.Wt<T>(L.XH) + (size_t)t * M * 192;
+  if constexpr (std::is_same<T, __bf16>::value)
+    if (t > 0) HIPCHK(xh_to_hr(M, xht, c.Wt<__bf16>(L.HR) + (size_t)(t - 1) * M * 128, c.st));
+  HIPCHK(reset_rows(c.reset + (size_t)t * L.B, L.B, L.P, ResetZerosT<T>{}.add(xht + 64, 192, 128), *cp, c.Wf(L.dC), 128,
+                    c.st));
   *cp = c.Wf(L.dC);
+  return AAA_OK;
+}
+// bf16 under a mask, after the last step of a per-step chain: h_{T-1} (XH slot T, which no step zeroes) -> HR
+template <typename T>
+static int hr_last(const CallCtx& c) {
+  if constexpr (std::is_same<T, __bf16>::value) {
+    const Layout& L = c.L;
+    const size_t M = (size_t)L.B * L.P;
+    if (c.reset) HIPCHK(xh_to_hr((long)M, c.Wt<__bf16>(L.XH) + (size_t)L.T * M * 192, c.Wt<__bf16>(L.HR) + (size_t)(L.T - 1) * M * 128, c.st));
+  }
   return AAA_OK;
 }
 
@@ -280,14 +296,23 @@ static int recur_frames_bf16(const CallCtx& c) {
                       nullptr, (GT*)(c.ws + L.Gt), (int*)(c.ws + L.rflags), L.T, L.B, L.h, L.w, L.P, rep,
                       pair_budget(L.T), rec_stagger("AAA_REC_STAGGER_FWD")};
   rp.cqm = c.plan.cqm;
+  if (c.reset) {   // the single-workgroup kernel's mask variant (recur.h RST; the plan sends no other here)
+    if (band || G != 1) return fail(AAA_E_LAUNCH, "episode-start masks: no paired or band-mode bf16 kernel takes one");
+    rp.reset = c.reset;
+    rp.HR = c.Wt<__bf16>(L.HR);
+    // slot 0's h half of the rows that start an episode at step 0: this launch's and the weight gradient's operand
+    if (c.io->h0)
+      HIPCHK(reset_rows(c.reset, L.B, L.P, ResetZerosT<__bf16>{}.add(c.Wt<__bf16>(L.XH) + 64, 192, 128), nullptr, nullptr, 0,
+                        c.st));
+  }
   // row-padded h image (recur.h rec_rowpad): measured neutral to 1 % slower (C3 forward 1234-1242 vs
   // 1247-1269 us, profiles/r06/ab/rowpad_fwd/), so an A/B option (AAA_REC_ROWPAD=1, ablation builds)
   if (!band) rp.rowpad = ab_int("AAA_REC_ROWPAD", 0) ? rec_rowpad(L.h, L.w) : 0;
   TimerScope tim(AAA_TIMER_FWD_STEP, c.st, 2.0 * M * 512 * 1728 * L.T,
                  band ? strf("bf16 band-mode frame-resident [x|h] recurrence, %d steps per launch, %d bands per frame "
                              "[kernel: k_convlstm_fwd_frames+Lb1E]", L.T, G)
-                      : strf("bf16 frame-resident [x|h] recurrence, %d steps per launch, %d WG per frame%s [kernel: k_convlstm_fwd_frames+Lb0E]",
-                             L.T, G, rp.rowpad ? ", row-padded h image" : ""));
+                      : strf("bf16 frame-resident [x|h] recurrence, %d steps per launch, %d WG per frame%s [kernel: k_convlstm_fwd_frames+Lb0E]%s",
+                             L.T, G, rp.rowpad ? ", row-padded h image" : "", c.reset ? ", resets" : ""));
   HIPCHK(band ? convlstm_fwd_frames_band<GT>(rp, c.st) : convlstm_fwd_frames<GT>(rp, G, c.st));
   return AAA_OK;
 }
@@ -301,7 +326,7 @@ static int recur_fused_steps(const CallCtx& c) {
   const int M = L.B * L.P;
   for (int t = 0; t < L.T; ++t) {   // ConvLSTM (attention.py:110-126), x- and h-part together
     const float* cp;
-    if (const int rc = c_in(c, t, &cp)) return rc;
+    if (const int rc = c_in<T>(c, t, &cp)) return rc;
     EpiConvLstmFwd<T, GT> ep{cp, c.Wf(L.Cst) + (size_t)(t + 1) * M * 128, hs_out(c, t),
                              c.Wt<T>(L.XH) + (size_t)(t + 1) * M * 192, (GT*)(c.ws + L.Gt) + (size_t)t * M * 512, M,
                              (const float*)(c.pk + L.k_bl)};
@@ -309,7 +334,7 @@ static int recur_fused_steps(const CallCtx& c) {
                                      c.st, L.dhs ? c.Wf(L.dhs) : nullptr, c.reset != nullptr);
     if (rc) return rc;
   }
-  return AAA_OK;
+  return hr_last<T>(c);
 }
 
 // The x-part of the ConvLSTM steps (not recurrent), batched: Gt <- Wx * x_t + b, in chunks of ``cs`` steps on
@@ -354,7 +379,7 @@ static int recur_xpart_steps(const CallCtx& c) {
   for (int t = 0; t < L.T; ++t) {  // ConvLSTM recurrence (attention.py:110-126): h-part only
     if (ax && t % cs == 0) HIPCHK(hipStreamWaitEvent(st, xev[t / cs], 0));   // x-part of steps [t, t+cs) done
     const float* cp;
-    if (const int rc = c_in(c, t, &cp)) return rc;
+    if (const int rc = c_in<T>(c, t, &cp)) return rc;
     if (t == 0 && !c.io->h0) {       // zero state: gates come from the x-part alone
       HIPCHK(gate_fwd_zx<T>(M, cp, c.Wf(L.Gt), c.Wf(L.Cst) + (size_t)M * 128, hs_out(c, 0),
                             c.Wt<T>(L.XH) + (size_t)M * 192, st));
@@ -373,7 +398,7 @@ static int recur_xpart_steps(const CallCtx& c) {
     });
     HIPCHK(e);
   }
-  return AAA_OK;
+  return hr_last<T>(c);
 }
 
 // The ConvLSTM recurrence on the plan's path, with fp16 or fp32 gate storage
@@ -452,7 +477,7 @@ static int forward_tail_stateful(const CallCtx& c) {
     // attention readout with this step's per-frame queries (basis logits in-kernel)
     {
       TimerScope tim(AAA_TIMER_ATTN_FWD, st, (double)B * attn_fwd_bytes(P, L.nq, L.ans_ld, L.esz), L.esz == 2 ? "k_attn_fwd_mfma, per-frame query (stateful core)" : "k_attn_fwd, per-frame query (stateful core)");
-      HIPCHK(attn_fwd(readout_h(L, c.ws).frame(f0, P), io->basis, Qt, nullptr, io->prev_reward ? io->prev_reward + f0 : nullptr,
+      HIPCHK(attn_fwd(readout_h(L, c.ws, c.reset != nullptr).frame(f0, P), io->basis, Qt, nullptr, io->prev_reward ? io->prev_reward + f0 : nullptr,
                       io->prev_action ? io->prev_action + f0 : nullptr, B, P, L.nq, c.Wf(L.Am) + f0 * P * L.nq,
                       c.Wf(L.ans) + f0 * L.ans_ld, L.ans_ld, st, qd));
     }
@@ -484,7 +509,7 @@ static int forward_tail_batched(const CallCtx& c) {
   }
   {
     TimerScope tim(AAA_TIMER_ATTN_FWD, st, (double)F * attn_fwd_bytes(P, L.nq, L.ans_ld, L.esz), L.esz == 2 ? "k_attn_fwd_mfma (readout on the MFMA, map and basis in bf16 parts), 1 WG per frame" : "k_attn_fwd (VALU), 1 WG per frame");
-    HIPCHK(attn_fwd(readout_h(L, c.ws), io->basis, Qc, c.Wf(L.SQ), io->prev_reward, io->prev_action, F, P, L.nq,
+    HIPCHK(attn_fwd(readout_h(L, c.ws, c.reset != nullptr), io->basis, Qc, c.Wf(L.SQ), io->prev_reward, io->prev_action, F, P, L.nq,
                     c.Wf(L.Am), c.Wf(L.ans), L.ans_ld, st));
   }
   TimerScope tim(AAA_TIMER_TAIL_FWD, st, (double)F * tail_fwd_flop(L), "answer MLP + LSTMCell + heads (fp32 GEMMs)");

@@ -238,6 +238,9 @@ int aaa_workspace_region(const aaa_cfg* cfg, int region, size_t* offset, size_t*
       else { *offset = L.Gt; *bytes = F * L.P * 512 * recur_plan(L, false).gate_bytes; }
       return AAA_OK;
     }
+    case AAA_BF16_WS_HR:   // h_t for the readout of a masked call: bf16 cfgs with AAA_FLAG_BF16_RESETS, the last region
+      if (!L.br) break;
+      *offset = L.HR; *bytes = F * L.P * 128 * 2; return AAA_OK;
     default: break;
   }
   return fail(AAA_E_ARG, "workspace_region: region %d not computed by this cfg", region);
@@ -406,9 +409,10 @@ int aaa_backward(const aaa_cfg* cfg, const aaa_io* io, int phases, hipStream_t s
 // Episode-start masks (include/aaa.h): what a mask cannot go with, refused before the device is touched.
 static int check_reset(const Layout& L, const float* reset, const char* who) {
   if (!reset) return AAA_OK;
-  if (L.dt == AAA_BF16)
-    return fail(AAA_E_ARG, "%s: an episode-start mask needs an fp32 cfg (the bf16 readout reads h_t from the [x | h] "
-                "operand slots, which a reset zeroes); pass reset = NULL and cut the unroll at episode ends", who);
+  if (L.dt == AAA_BF16 && !L.br)
+    return fail(AAA_E_ARG, "%s: an episode-start mask needs an fp32 cfg, or a bf16 cfg with AAA_FLAG_BF16_RESETS (the "
+                "bf16 readout reads h_t from the [x | h] operand slots, which a reset zeroes; the flag adds a copy "
+                "for it); or pass reset = NULL and cut the unroll at episode ends", who);
   if (!aligned16(reset)) return fail(AAA_E_ALIGN, "%s: the reset mask must be 16-byte aligned", who);
   return AAA_OK;
 }
@@ -427,7 +431,8 @@ int aaa_forward_resets(const aaa_cfg* cfg, const aaa_io* io, int phases, const f
   if ((r = check_device())) return r;
   if ((r = check_io(L, io, false))) return r;
   if (!(cfg->flags & AAA_FLAG_DEFER_STRANDED) && (r = pair_check())) return r;
-  return forward_impl<float>(L, io, stream, phases, reset);
+  return L.dt == AAA_BF16 ? forward_impl<__bf16>(L, io, stream, phases, reset)
+                          : forward_impl<float>(L, io, stream, phases, reset);
 }
 
 int aaa_backward_resets(const aaa_cfg* cfg, const aaa_io* io, int phases, const float* reset, hipStream_t stream) {
@@ -440,7 +445,8 @@ int aaa_backward_resets(const aaa_cfg* cfg, const aaa_io* io, int phases, const 
   if ((r = check_io(L, io, true))) return r;
   if (phases & ~AAA_BWD_ALL || !phases) return fail(AAA_E_ARG, "bad phase mask %d", phases);
   if (!(cfg->flags & AAA_FLAG_DEFER_STRANDED) && (r = pair_check())) return r;
-  return backward_impl<float>(L, io, phases, stream, reset);
+  return L.dt == AAA_BF16 ? backward_impl<__bf16>(L, io, phases, stream, reset)
+                          : backward_impl<float>(L, io, phases, stream, reset);
 }
 
 int aaa_pair_status(hipStream_t stream, int clear) {

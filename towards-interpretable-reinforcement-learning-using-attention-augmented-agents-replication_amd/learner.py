@@ -63,7 +63,8 @@ class Learner:
                  dtype: str = "fp32", device=None, seed: int = 0, group=None, lr: float = 1e-3,
                  frames_u8: bool = False, max_grad_norm: float | None = None, optimizer: str = "adam",
                  rmsprop: dict | None = None, lr_anneal_steps: int = 0, lr_end: float = 0.0,
-                 stateful_core: bool = False):
+                 stateful_core: bool = False, resets: bool = False):
+        # resets: a bf16 learner whose step methods take reset= (UnrollRunner(resets=True)); fp32 learners take it anyway
         if optimizer not in ("adam", "rmsprop"):
             raise ValueError(f"Learner: optimizer must be 'adam' or 'rmsprop' (got {optimizer!r})")
         if optimizer == "adam" and lr_anneal_steps:
@@ -76,7 +77,7 @@ class Learner:
             raise ValueError(f"Learner: unknown rmsprop setting(s) {sorted(unknown)}; known: "
                              f"{sorted(self.RMSPROP_DEFAULTS)}")
         self.runner = r = UnrollRunner(B, T, H, W, nq, A, dtype, device, stateful_core=stateful_core,
-                                       frames_u8=frames_u8, defer_stranded=True)
+                                       frames_u8=frames_u8, defer_stranded=True, resets=resets)
         self.device = r.device
         params = detinit.deterministic_params(seed, A, nq)
         self.flat = torch.from_numpy(np.concatenate([v.reshape(-1) for v in params.values()])).to(self.device)
@@ -136,7 +137,8 @@ class Learner:
         overlaps the vision backward and never runs beside a frame-resident
         launch.  ``comm_timing`` records per-bucket events; read them with
         comm_stats() after a sync.  ``reset``: None, or a (T, B) episode-start
-        mask on the device (``UnrollRunner.forward``; fp32 learners).
+        mask on the device (``UnrollRunner.forward``; fp32 learners, and bf16
+        learners built with ``resets=True``).
         ``initial_state``: None (the unroll starts from ``reset()``), or the
         state before step 0 as the actor held it -- ``(h0, c0)`` (B, h, w, 128),
         with a stateful core ``(h0, c0, core_h0, core_c0)``, the last two
@@ -400,12 +402,12 @@ class Learner:
         """One complete iteration on an unroll the actors recorded
         (``UnrollCollector.take()``, unroll.py): train_step_vtrace() on its
         buffers with ``bootstrap="last"``, from the state the actors held before
-        its step 0.  fp32 learners also cut the state at the episode ends inside
-        it (``reset="done"`` with the unroll's ``first``); bf16 learners refuse a
-        reset mask and get the initial state alone (its rows of ``first`` hold
-        the reset() state already: the recorder stores the state after the
-        episode-start reset)."""
-        if self.runner.dtype == "fp32":
+        its step 0.  fp32 learners, and bf16 learners built with ``resets=True``,
+        also cut the state at the episode ends inside it (``reset="done"`` with
+        the unroll's ``first``); other bf16 learners refuse a reset mask and get
+        the initial state alone (its rows of ``first`` hold the reset() state
+        already: the recorder stores the state after the episode-start reset)."""
+        if self.runner.dtype == "fp32" or self.runner.resets:
             hparams = dict(hparams, reset="done", first=unroll.first)
         return self.train_step_vtrace(unroll.frames, unroll.actions, unroll.rewards, unroll.logp, unroll.done,
                                       bootstrap="last", initial_state=unroll.initial_state, **hparams)

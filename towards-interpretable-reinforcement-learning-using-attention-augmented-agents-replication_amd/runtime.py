@@ -16,7 +16,9 @@ from . import _native as N
 class UnrollRunner:
     def __init__(self, B: int, T: int, H: int, W: int, nq: int = 4, A: int = 18,
                  dtype: str = "fp32", device=None, stateful_core: bool = False, frames_u8: bool = False,
-                 defer_stranded: bool = False):
+                 defer_stranded: bool = False, resets: bool = False):
+        """``resets``: a bf16 runner that takes episode-start masks (``reset=`` of forward / backward;
+        AAA_FLAG_BF16_RESETS: one more workspace region, nothing else changes).  fp32 runners take them anyway."""
         if dtype not in ("fp32", "bf16"):
             raise ValueError(f"dtype must be 'fp32' or 'bf16', got {dtype!r}")
         self.lib = N.load()
@@ -27,7 +29,9 @@ class UnrollRunner:
         self.frames_u8 = bool(frames_u8)
         self.cfg = N.Cfg(B, T, H, W, nq, A, N.BF16 if dtype == "bf16" else N.F32,
                          (N.FLAG_STATEFUL_CORE if stateful_core else 0) | (N.FLAG_FRAMES_U8 if frames_u8 else 0)
-                         | (N.FLAG_DEFER_STRANDED if defer_stranded else 0))
+                         | (N.FLAG_DEFER_STRANDED if defer_stranded else 0)
+                         | (N.FLAG_BF16_RESETS if resets else 0))
+        self.resets = bool(resets)
         self.B, self.T, self.H, self.W, self.nq, self.A, self.dtype = B, T, H, W, nq, A, dtype
         self.h, self.w = N.grid(H, W)
         self.P = self.h * self.w
@@ -105,7 +109,8 @@ class UnrollRunner:
         ``core`` = (h0, c0) or zeros.  ``phases`` = FWD_VISION | FWD_TAIL skips
         the ConvLSTM recurrence (its products imported first: core_import).
         ``reset`` (T, B): rows with reset[t][b] != 0 enter step t from the
-        reset() state (aaa_forward_resets; fp32 runners); pass the same mask
+        reset() state (aaa_forward_resets; fp32 runners, and bf16 runners built
+        with ``resets=True``); pass the same mask
         to ``backward``."""
         T, B, A = self.T, self.B, self.A
         dev = self.device
